@@ -24,11 +24,15 @@ Prints ONE JSON line on rank 0:
   eval                  validation (`test()`, packed rows) and whole-utterance inference (`predict_utterance`, T up to ~1000: per-tile attention)
   pipeline              the per-batch device loader (DeviceBatchBuilder: raw recordings + audio -> batch dict), frames/s vs the host chain
 --scaling strong deals ONE reference-size batch over the ranks by length (default: weak, a batch per rank).
+--dump-outputs DIR writes what the last timed step computed (rank 0) as DIR/<name>.npy: loss, phoneme_accuracy, pred (mel prediction),
+phoneme_logits, and fixed seeded samples of the updated parameter and gradient arenas.  Inputs are seeded (batches, weights, dropout,
+shift augmentation), so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes
 import json
 import os
+import random
 import sys
 import time
 
@@ -238,11 +242,12 @@ def csrc_fingerprint():
     return h.hexdigest()[:16]
 
 
-def make_step(model, optim, batches, dp, it):
+def make_step(model, optim, batches, dp, it, keep=None):
     """One training step per call, on batches[it % len(batches)]: the timed loop ROTATES distinct reference-size batches, so every step
     hands the path tensors it has not seen the step before -- the per-batch host work (pack tables, loss plan, their upload) is paid
     every step exactly as reference transduction_model.py:196-212 pays it for every DataLoader batch.  (Nothing in the package caches
-    per-batch state across steps any more; a single-element list reproduces the old same-batch loop for the `same_batch` figure.)"""
+    per-batch state across steps any more; a single-element list reproduces the old same-batch loop for the `same_batch` figure.)
+    `keep` (a dict) receives the step's outputs (references only, no copies or synchronisation) for --dump-outputs."""
     from silent_speech_amd.transduction_model import dtw_loss, prepare_batch
     if isinstance(batches, dict):
         batches = [batches]
@@ -259,12 +264,14 @@ def make_step(model, optim, batches, dp, it):
             dp.begin_step(X_raw.shape[0] * 200, dp.local_target_frames(batch))
         pred, aux = model(X, X_raw, sess)
         total = dp.global_total(batch) if dp is not None else None
-        loss, _ = dtw_loss(pred, aux, batch, phoneme_loss_weight=0.5, total_length=total)
+        loss, acc = dtw_loss(pred, aux, batch, phoneme_loss_weight=0.5, total_length=total)
         loss.backward()
         if dp is not None:
             dp.sync_gradients(model)
         optim.step()
         it[0] += 1
+        if keep is not None:
+            keep.update(loss=loss, acc=acc, pred=pred, aux=aux)
         return loss
     return step
 
@@ -539,6 +546,36 @@ def launch_ranks(args):
     return 1
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_ARENA_SAMPLE = 1 << 20          # elements of the parameter / gradient arenas written by --dump-outputs
+
+
+def dump_outputs(out_dir, keep, model):
+    """--dump-outputs: the arrays the last timed step handed its caller, as float32 / float64 .npy files.  pred and phoneme_logits
+    are whole (packed rows x 200 frames); the parameter and gradient arenas (~53 M floats each) are sampled at the same fixed,
+    seeded, sorted positions on every run."""
+    import numpy as np
+    flat, gflat, n = model.flat_arenas()
+    idx = np.unique(np.random.default_rng(0).integers(0, n, DUMP_ARENA_SAMPLE))
+    idx_dev = torch.from_numpy(idx).to(flat.device)
+    arrays = {'loss': keep['loss'].detach().double().cpu().numpy().reshape(()),
+              'phoneme_accuracy': keep['acc'].detach().double().cpu().numpy().reshape(()),
+              'pred': keep['pred'].detach().float().cpu().numpy(),
+              'phoneme_logits': keep['aux'].detach().float().cpu().numpy(),
+              'params_sample': flat.index_select(0, idx_dev).cpu().numpy(),
+              'grads_sample': gflat.index_select(0, idx_dev).cpu().numpy()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit('--dump-outputs: %d bytes exceed the %d-byte limit' % (total, DUMP_LIMIT_BYTES))
+    if not os.path.isdir(out_dir):
+        os.makedirs(out_dir)
+        with open(os.path.join(out_dir, '.gitignore'), 'w') as f:         # a dump made inside a checkout leaves `git status` clean
+            f.write('*\n')
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return {'dir': os.path.abspath(out_dir), 'arrays': sorted(arrays), 'bytes': total}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -554,7 +591,10 @@ def main():
     ap.add_argument('--no-legs', action='store_true', help='skip the DTW (configs[2]), mel, fp32-mode, CTC (configs[4]), eval and pipeline legs')
     ap.add_argument('--scaling', default='weak', choices=['weak', 'strong'], help='weak: one reference-size batch per rank; strong: ONE such batch dealt over the ranks by length')
     ap.add_argument('--cpu-full', type=int, default=1, help='also time the CPU baseline on the FULL batch (1 warm-up + 2 timed steps, ~1 min); 0 = sample only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write the outputs of the last timed step to DIR/<name>.npy (rank 0)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -592,6 +632,7 @@ def main():
     torch.manual_seed(0)
     model = Model(112, 80, 48, model_size=768, num_layers=6, dropout=0.2, compute_dtype=dt, f32_matmul='bf16x3' if args.dtype == 'fp32x3' else 'exact').to(dev)
     model.train()
+    model.shift_rng = random.Random(rank)          # the shift augmentation draws (architecture.py:65) are seeded like everything else
     init_sd = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
     dp = DataParallel() if world > 1 else None
     if dp is not None:
@@ -616,12 +657,13 @@ def main():
     frames = frames_of[0]
     rows = (frames + 199) // 200
     it = [0]
-    step = make_step(model, optim, batches, dp, it)
+    keep = {} if args.dump_outputs and rank == 0 else None
+    step = make_step(model, optim, batches, dp, it, keep)
 
     for _ in range(args.warmup):
         loss = step()
     torch.cuda.synchronize()
-    if not torch.isfinite(loss.detach()).item():
+    if args.warmup and not torch.isfinite(loss.detach()).item():
         raise SystemExit('non-finite loss after warm-up')
     plan = engine.plan_binding(model)
     L = _lib.lib()
@@ -662,6 +704,7 @@ def main():
     elapsed = time.perf_counter() - t0
     ops.PROFILER = None
     final_loss = float(loss.detach())
+    dumped = dump_outputs(args.dump_outputs, keep, model) if keep is not None else None          # before the comparison loops train on
     comm = None
     if dp is not None:
         exposed = dp.exposed_ms()
@@ -752,6 +795,8 @@ def main():
         }
         if comm is not None:
             out.update(comm)
+        if dumped is not None:
+            out['dump_outputs'] = dumped
         if prof is not None:
             psteps = len(range(0, args.steps, pstride))
             rows_buf = (_lib.ProfileRow * 64)()

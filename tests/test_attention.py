@@ -1,6 +1,7 @@
 """Fused relative-position attention (forward + backward) vs the closed-form fp32 torch restatement
 (oracle/model_ref.relpos_logits, itself pinned to the reference's pad/view skew by golden vectors)."""
 import math
+import os
 
 import pytest
 import torch
@@ -117,9 +118,18 @@ def test_attention_transposed_score_kernels(dev, case, p):
     _run(dev, torch.bfloat16, B=2, H=2 if is_emu(dev) else 8, T=T, dh=dh, D=D, seed=T + D, tol_f=2e-2, tol_b=3e-2, p=p)
 
 
-def _need_res16(monkeypatch, T, dp, D):
-    """The LDS-resident 16 x 16 family (rounds 1-4) lives only in A/B builds of the library (-DSS_ATTN_RES16, tools/measure_lib.sh) since round 6."""
+RES16_HIP = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'silent_speech_amd', 'lib', 'libsilent_speech_hip_res16.so')
+
+
+def _need_res16(dev, monkeypatch, T, dp, D):
+    """The LDS-resident 16 x 16 family (rounds 1-4) lives only in A/B builds of the library (-DSS_ATTN_RES16) since round 6: on the GPU the
+    test runs on build()'s libsilent_speech_hip_res16.so (the product sources with that family compiled in); the product library returns
+    after the test."""
     monkeypatch.setenv('SS_ATTN_T', '0')
+    if not is_emu(dev):
+        from silent_speech_amd import _lib
+        monkeypatch.setattr(_lib, '_lib', _lib.lib())
+        _lib.load(RES16_HIP)
     if ops.relpos_attention_family(torch.bfloat16, T, dp, D) != 1:
         pytest.skip('the 16 x 16 resident attention kernels are compiled only into A/B builds (-DSS_ATTN_RES16)')
 
@@ -129,7 +139,7 @@ def _need_res16(monkeypatch, T, dp, D):
 def test_attention_resident_16x16_kernels_still_agree(dev, monkeypatch, dt_old):
     """SS_ATTN_T=0 keeps the LDS-resident 16 x 16 kernels of rounds 1-4 reachable (A/B measurements): same function."""
     dev_T, dev_dp, dev_D = (37, 32, 9) if is_emu(dev) else (200, 96, 100)
-    _need_res16(monkeypatch, dev_T, dev_dp, dev_D)
+    _need_res16(dev, monkeypatch, dev_T, dev_dp, dev_D)
     if is_emu(dev):
         _run(dev, dt_old, B=1, H=2, T=37, dh=8, D=9, seed=1, tol_f=2e-2, tol_b=3e-2, p=0.25)
     else:
@@ -223,7 +233,7 @@ def test_resident_forward_generations_agree(dev, monkeypatch, T, D, dh, p):
         pytest.skip('full-size rows: gpu tier')
     B, H, dt = 2, 2, torch.bfloat16
     dp, Tp = (dh + 31) // 32 * 32, (T + 7) // 8 * 8
-    _need_res16(monkeypatch, T, dp, D)                   # the 16 x 16 resident kernels (rounds 1-4), kept behind this switch in A/B builds
+    _need_res16(dev, monkeypatch, T, dp, D)                   # the 16 x 16 resident kernels (rounds 1-4), kept behind this switch in A/B builds
     g = torch.Generator().manual_seed(7)
     qkv = (torch.randn(B * T, 3 * H * dp, generator=g) * 0.7).to(dt)
     E = (torch.randn(H, 2 * D - 1, dp, generator=g) * dh ** -0.5).to(dt)
@@ -244,11 +254,13 @@ def test_persistent_per_head_schedule_equals_one_workgroup_per_pair(dev, monkeyp
     is the old one-workgroup-per-pair launch.  Same arithmetic per pair: output, lse, the probability image and dqkv must be bit-identical."""
     # emulator: 4 "CUs".  (5, 2): 2 workgroups per head, 2 whole sequences each + one split in halves; (6, 2): no partial round; (5, 1): 4 workgroups,
     # two of them without a half; (7, 1): 3 left over of 4 -> not split (a second whole round for three workgroups).  GPU: the benchmarked launch.
-    if not is_emu(dev) and BH != (5, 2):
-        pytest.skip('emulator-size schedules')
-    B, H, T, dh, D = (BH[0], BH[1], 40, 32, 9) if is_emu(dev) else (110, 8, 200, 96, 100)
+    # GPU: the same cases at the device's CU count -- (5, 2): the benchmarked launch (880 pairs); (6, 2): whole rounds only; (5, 1): a quarter round
+    # left over, split in halves; (7, 1): three quarters left over, not split.
+    cus = 4 if is_emu(dev) else torch.cuda.get_device_properties(dev).multi_processor_count
+    gpu_B = {(5, 2): 110, (6, 2): cus // 4, (5, 1): cus + cus // 4, (7, 1): cus + 3 * cus // 4}[BH]
+    B, H, T, dh, D = (BH[0], BH[1], 40, 32, 9) if is_emu(dev) else (gpu_B, 8 if BH[1] == 2 else 1, 200, 96, 100)
     dt, dp, Tp = torch.bfloat16, (dh + 31) // 32 * 32, (T + 7) // 8 * 8
-    _need_res16(monkeypatch, T, dp, D)                   # a schedule of the 16 x 16 resident kernels
+    _need_res16(dev, monkeypatch, T, dp, D)                   # a schedule of the 16 x 16 resident kernels
     g = torch.Generator().manual_seed(17)
     qkv = (torch.randn(B * T, 3 * H * dp, generator=g) * 0.7).to(dt).to(dev)
     E = (torch.randn(H, 2 * D - 1, dp, generator=g) * dh ** -0.5).to(dt)
