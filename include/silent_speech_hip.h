@@ -30,9 +30,9 @@ extern "C" {
 const char* ss_last_error(void);
 /* Library/ABI version and the GPU architecture the kernels were compiled for ("gfx950"). */
 /* Bumped whenever a struct layout or an entry-point signature changes (3: ss_gemm_epilogue column-statistics fields, the plan /
- * attention-image / LayerNorm-workspace entry points, ss_dtw_cumulative; 4: ss_loss_index_tables; 5: gate recomputation arguments of ss_bn_backward_sums / ss_bn_backward_apply; 7: ss_split_planes / ss_gemm_planes, ss_dw_job.flags, up to 24 jobs per grouped launch; 8: ss_stft_logmel_fft, the rejected-frame counter behind the matrix of ss_phoneme_confusion; 9: planes_hi / planes_lo / planes_only of ss_gemm_epilogue, dropout groups of the GEMM epilogue are row-major).  Bindings must compare it with SS_ABI_VERSION at load time: a stale
+ * attention-image / LayerNorm-workspace entry points, ss_dtw_cumulative; 4: ss_loss_index_tables; 5: gate recomputation arguments of ss_bn_backward_sums / ss_bn_backward_apply; 7: ss_split_planes / ss_gemm_planes, ss_dw_job.flags, up to 24 jobs per grouped launch; 8: ss_stft_logmel_fft, the rejected-frame counter behind the matrix of ss_phoneme_confusion; 9: planes_hi / planes_lo / planes_only of ss_gemm_epilogue, dropout groups of the GEMM epilogue are row-major; 10: ss_emg_features_batch).  Bindings must compare it with SS_ABI_VERSION at load time: a stale
  * library paired with newer headers would otherwise read garbage struct fields instead of failing. */
-#define SS_ABI_VERSION 9
+#define SS_ABI_VERSION 10
 int ss_abi_version(void);
 const char* ss_target_arch(void);
 
@@ -457,6 +457,12 @@ int ss_iir_filtfilt_batch(const double* x, double* y, const int32_t* lengths_hos
 /* np.interp of every recording onto its own grid; table_dev: int64 [R][4] = {first input row, T, first output row, T_out}. */
 int ss_linear_resample_batch(const double* x, double* y, const int64_t* table_dev, int R, int C, double old_freq, double new_freq,
                              int64_t total_out_rows, void* stream);
+/* The 14 hand-crafted features per channel of data_utils.get_emg_features (data_utils.py:85-136) for a RAGGED BATCH in one launch: x packed
+ * (sum n_u, C) f64 at 516.79 Hz (what ss_linear_resample_batch wrote), out packed (total_frames, 14 C) f32, column c * 14 + j = {mean(w),
+ * rms(w), rms(|p|), zero-crossing rate of p, mean(|p|), |rfft(hann16 * xs)| bins 0..8} of the frames [6 f, 6 f + 16), where xs = x - its
+ * column mean, w = the 9-tap box filter applied twice ('same', each pass zero-padding its own input) and p = xs - w; f64 arithmetic, f32
+ * store.  table_dev: int64 [R][4] = {first input row, n, first output row, F = n < 16 ? 0 : 1 + (n - 16) / 6}.  1 <= C <= 32. */
+int ss_emg_features_batch(const double* x, float* out, const int64_t* table_dev, int R, int C, int64_t total_frames, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The execution plan of the transduction model as native code: ONE call enqueues the whole forward pass of Model.forward

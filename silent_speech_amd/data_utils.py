@@ -1,6 +1,7 @@
 """Drop-in for the hot-path parts of the reference's data_utils.py:
 
     mel_spectrogram(y, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, center=False)   (:39-62)
+    get_emg_features(emg_data, debug=False)                                                            (:85-136)
     combine_fixed_length(tensor_list, length) / decollate_tensor(tensor, lengths)                      (:158-178)
     FeatureNormalizer                                                                                   (:138-156)
     phoneme_inventory                                                                                   (:17)
@@ -254,6 +255,25 @@ def mel_spectrogram_batch(signals, n_fft=1024, num_mels=80, sampling_rate=22050,
                                                 _lib.stream_of(flat)), 'ss_reflect_pad_ragged')
     _stft_logmel(ypad, B, F, ldp, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, out, frame_major=True)
     return out, frames
+
+
+def get_emg_features(emg_data, debug=False):
+    """data_utils.py:85-136: (n, C) EMG at 516.79 Hz -> (1 + (n - 16) // 6, 14 C) float32 hand-crafted features (per channel: frame mean
+    and RMS of the twice box-filtered signal w, RMS / mean / zero-crossing rate of the residual p = x - mean - w, 9 |rfft| bins of the
+    Hann-windowed frame).  A numpy array in gives a numpy array out; a tensor gives a tensor on its device.  Computed in f64 on the device by
+    csrc/emg_features.hip through torch.ops.silent_speech.emg_features (torch_ops.py).  debug=True (the reference's matplotlib plots) is
+    not supported."""
+    if debug:
+        raise NotImplementedError('get_emg_features(debug=True): the diagnostic plots are not part of this package')
+    from .read_emg import _to_device_2d
+    if np.ndim(emg_data) != 2:
+        raise ValueError('emg_data must be (samples, channels)')
+    if emg_data.shape[0] < 16:
+        raise ValueError('Input is too short (n=%d) for frame_length=16' % emg_data.shape[0])      # librosa.util.frame raises
+    x, restore = _to_device_2d(emg_data)
+    from . import torch_ops  # noqa: F401
+    y = torch.ops.silent_speech.emg_features(x)
+    return y.cpu().numpy() if not torch.is_tensor(emg_data) else y
 
 
 class FeatureNormalizer(object):

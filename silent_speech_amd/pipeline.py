@@ -6,8 +6,9 @@ load_utterance / load_audio do on the CPU per utterance (and lru_cache), done on
     mel_targets(audio, normalizer, ...)     data_utils.py:64-83 + read_emg.py:231   clip -> mel_spectrogram (HIP DFT/mel GEMMs) -> (T, 80) -> normalise
     ShardedSizeAwareSampler                 read_emg.py:115-140   greedy length-budget batches, dealt round-robin to the DP ranks
 
-File decoding, resampling of 16 kHz audio and the offline EMG filters (read_emg.py:27-71) stay on the host (row N4 /
-out of scope); everything here starts from arrays already in memory.  All functions keep the data on the device and
+File decoding and resampling of 16 kHz audio stay on the host (out of scope); the offline EMG filters (read_emg.py:27-71) and the
+hand-crafted EMG features (data_utils.py:85-136) run in DeviceBatchBuilder on the device; everything here starts from arrays already in
+memory.  All functions keep the data on the device and
 enqueue on the current stream; nothing synchronises.
 """
 import random
@@ -188,14 +189,21 @@ class DeviceBatchBuilder(object):
                 launch -> /20, 50 tanh(./50) (:227-228) in one kernel
         audio : clip + reflect pad (ragged) -> one hop-strided DFT GEMM -> |.| -> one mel GEMM + log clamp -> FeatureNormalizer, all
                 utterances at once (data_utils.mel_spectrogram_batch); truncation to n frames is a view
-    The 112-d hand-crafted EMG features (`emg`, data_utils.py:92-136) are not inputs of the model (architecture.py:61 ignores
-    x_feat) and are emitted as zeros of the right shape unless the recording brings `emg_features`."""
+        features: (emg_features=True) the voiced twins' raw EMG joins the same filter launch sequence, one more resample launch gives
+                the 516.79 Hz signals (:71) of own recordings and twins, their remove_channels columns are zeroed (:73-75), ONE launch
+                computes the 112-d features of all of them (csrc/emg_features.hip, data_utils.py:85-136) and, with emg_norm, one soft clip
+                normalises the packed result (:231-233); `emg` / `parallel_voiced_emg` are views truncated to each recording's frames
+    The 112-d hand-crafted EMG features (`emg`, data_utils.py:92-136) are not inputs of the model (architecture.py:61 ignores x_feat), so
+    by default they are emitted as zeros of the right shape; a recording that brings `emg_features` has them passed through (normalised
+    with emg_norm), with or without emg_features=True."""
 
-    def __init__(self, device, mfcc_norm=None, emg_norm=None, limit_length=False, sil_index=0, remove_channels=()):
+    def __init__(self, device, mfcc_norm=None, emg_norm=None, limit_length=False, sil_index=0, remove_channels=(), emg_features=False):
         """remove_channels: the reference's FLAGS.remove_channels (read_emg.py:73-75): those raw-EMG columns are zeroed after the
-        filtering / resampling and before the soft clip, exactly where load_utterance does it."""
+        filtering / resampling and before the soft clip, exactly where load_utterance does it.  emg_features: compute `emg` /
+        `parallel_voiced_emg` from the raw EMG like load_utterance (read_emg.py:78) instead of emitting zeros."""
         self.device, self.mfcc_norm, self.emg_norm, self.limit_length, self.sil_index = torch.device(device), mfcc_norm, emg_norm, limit_length, sil_index
         self.remove_channels = tuple(int(c) for c in remove_channels)
+        self.emg_features = bool(emg_features)
 
     # ---- host arrays of a batch in ONE pinned copy (round 5: the leg was host-bound -- 123 small uploads and ~100 glue launches per batch)
     @staticmethod
@@ -207,9 +215,9 @@ class DeviceBatchBuilder(object):
             x = x.detach().numpy()
         return np.ascontiguousarray(np.asarray(x), dtype=dtype)
 
-    # ---- EMG: every recording of the batch through ONE filter / resample launch sequence
-    def _filtered_689(self, recordings, packed=None):
-        from .read_emg import butter_highpass_coeffs, filtfilt_cascade_batch, iirnotch_coeffs, subsample_batch
+    # ---- EMG: every recording of the batch through ONE filter launch sequence -> the cropped 1 kHz signals
+    def _filtered_1k(self, recordings, packed=None):
+        from .read_emg import butter_highpass_coeffs, filtfilt_cascade_batch, iirnotch_coeffs
         dev = self.device
         sigs, cuts = [], []
         for rec in recordings:
@@ -222,8 +230,22 @@ class DeviceBatchBuilder(object):
         if filters is None:                                                                 # the same eight sections for every batch
             filters = DeviceBatchBuilder._filters = [iirnotch_coeffs(60 * h, 30, 1000) for h in range(1, 8)] + [butter_highpass_coeffs(3, 2, 1000)]
         ys = filtfilt_cascade_batch(filters, sigs if packed is None else packed)           # :67-68
-        ys = [y[nb:y.shape[0] - na] for y, (nb, na) in zip(ys, cuts)]                      # :69
-        return subsample_batch(ys, 689.06, 1000)                                           # :70
+        return [y[nb:y.shape[0] - na] for y, (nb, na) in zip(ys, cuts)]                     # :69
+
+    def _features(self, ys):
+        """The 1 kHz signals of own recordings and twins -> their normalised 112-d features, views of one packed buffer (read_emg.py:71-78,
+        231-233): one resample launch, remove_channels, one feature launch, one soft clip."""
+        from .read_emg import emg_features_batch, subsample_batch
+        e516 = subsample_batch(ys, 516.79, 1000)                                           # :71
+        x = e516[0]._base if e516[0]._base is not None else e516[0]
+        for ch in self.remove_channels:                                                     # :73-75, before get_emg_features (:78)
+            x[:, ch].zero_()
+        feats = emg_features_batch(e516)                                                   # :78 (data_utils.py:85-136)
+        if self.emg_norm is not None:                                                       # :231-233, in place over the packed buffer
+            y = feats[0]._base if feats[0]._base is not None else feats[0]
+            mean, std = _normalizer_tensors(self.emg_norm, y.shape[-1], self.device)
+            _soft_clip(y, y, y.shape[-1], mean, std, 1.0, 8.0)
+        return feats
 
     def _frames(self, rec, mel_frames, limit):
         n = min(_feature_frames(len(rec['raw_emg'])), mel_frames)
@@ -235,17 +257,23 @@ class DeviceBatchBuilder(object):
         # audio of every recording whose mel frames are needed: own audio (lengths; targets when voiced) and the voiced twins
         twins = [r['parallel'] if r['silent'] else None for r in recordings]
         audio_src = list(recordings) + [t for t in twins if t is not None]
+        # with emg_features: the twins whose features are computed here ride along in the EMG chain (after the own recordings)
+        feat_twins = [i for i, t in enumerate(twins) if self.emg_features and t is not None and t.get('emg_features') is None]
+        emg_src = list(recordings) + [twins[i] for i in feat_twins]
         # everything that arrives in host memory crosses PCIe in one pinned copy per kind (staging.upload).  The raw EMG goes first, on the main
         # stream, with its filter chain right behind it (~50 short, latency-bound launches: the critical path of a build); the audio is then
         # copied into its pinned buffer WHILE that chain runs, uploaded on a SIDE stream, and its half (clip, reflect pad, DFT / mel GEMMs,
         # normalise) runs there under the EMG half: the two are independent until the batch dict is assembled
         a_host = [self._host(r['audio'], np.float32) for r in audio_src]
-        e_host = [[self._host(p, np.float64) for p in (r.get('raw_emg_before'), r['raw_emg'], r.get('raw_emg_after')) if p is not None and len(p)] for r in recordings]
+        e_host = [[self._host(p, np.float64) for p in (r.get('raw_emg_before'), r['raw_emg'], r.get('raw_emg_after')) if p is not None and len(p)] for r in emg_src]
         emg_packed = None
         if all(p is not None for ps in e_host for p in ps):
             e_rows = [sum(int(p.shape[0]) for p in ps) for ps in e_host]
             emg_packed = (staging.upload([[p.reshape(p.shape[0], -1) for ps in e_host for p in ps]], dev)[0], e_rows)
-        e689 = self._filtered_689(recordings, emg_packed)
+        from .read_emg import subsample_batch
+        ys = self._filtered_1k(emg_src, emg_packed)
+        e689 = subsample_batch(ys[:len(recordings)], 689.06, 1000)                         # read_emg.py:70
+        efeat = self._features(ys) if self.emg_features else None
         side = None
         if dev.type == 'cuda':
             side = getattr(self, '_side', None)
@@ -310,23 +338,26 @@ class DeviceBatchBuilder(object):
             ph_host.append(ph)
             sess_host.append(np.full((n,), int(r.get('session_index', 0)), dtype=np.int64))
         ph_all, sess_all = staging.upload([ph_host, sess_host], dev)
-        zeros = torch.zeros(sum(n_own), 112, dtype=torch.float32, device=dev)
+        zeros = torch.zeros(sum(n_own), 112, dtype=torch.float32, device=dev) if efeat is None else None
+        twin_feats = {i: efeat[len(recordings) + k] for k, i in enumerate(feat_twins)}
         po = so = 0
         for i, (r, n) in enumerate(zip(recordings, n_own)):
             nt, feats = meta[i]
             ef = r.get('emg_features')
             if ef is None:
-                emg = zeros[so:so + n]
+                emg = zeros[so:so + n] if efeat is None else efeat[i][:n]                  # read_emg.py:82-83: truncated to the frame count
             else:
                 emg = torch.as_tensor(ef, dtype=torch.float32)[:n].to(dev)
                 emg = normalize_features(emg, self.emg_norm, 8.0) if self.emg_norm is not None else emg
             text = torch.as_tensor(r.get('text_int', np.zeros(0, dtype=np.int64)), dtype=torch.int64)
             out['audio_features'].append(feats); out['audio_feature_lengths'].append(nt)
             out['emg'].append(emg); out['raw_emg'].append(raw_views[i])
-            # read_emg.py:250-257: for a silent example the voiced twin's (normalised, soft-clipped) EMG features; np.zeros(1) otherwise.  The
-            # 112-d hand-crafted features are not computed here (not model inputs): the twin's are passed through when the recording brings them.
+            # read_emg.py:250-257: for a silent example the voiced twin's (normalised, soft-clipped) EMG features; np.zeros(1) otherwise.  Without
+            # emg_features=True they are not computed (not model inputs): the twin's are passed through when the recording brings them.
             pv = np.zeros(1)
-            if r['silent'] and r['parallel'].get('emg_features') is not None:
+            if i in twin_feats:
+                pv = twin_feats[i][:nt]                                                     # the twin's own frame count (load_utterance, :245)
+            elif r['silent'] and r['parallel'].get('emg_features') is not None:
                 pv = torch.as_tensor(r['parallel']['emg_features'], dtype=torch.float32).to(dev)
                 pv = normalize_features(pv, self.emg_norm, 8.0) if self.emg_norm is not None else pv
             out['parallel_voiced_emg'].append(pv)

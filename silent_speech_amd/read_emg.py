@@ -7,11 +7,14 @@
     subsample(signal, new_freq, old_freq)         read_emg.py:40-44   np.interp onto the new grid
     apply_to_all(function, signal_array, ...)     read_emg.py:46-50   per-channel application
     condition_raw_emg_recording(x)                read_emg.py:65-70   the whole chain of load_utterance on a (T, 8) recording
+    emg_features_batch(signals_516)               read_emg.py:78      data_utils.get_emg_features for a ragged batch, one launch
 
 The filters are designed here (closed forms of scipy.signal.iirnotch / butter / lfilter_zi, f64) and run by csrc/filters.hip; all
 channels of a recording go through ONE cascade launch, so `apply_to_all(notch_harmonics, x, 60, 1000)` costs the same as one channel.
 Inputs may be numpy arrays or tensors; the arithmetic is f64 on the device and results come back in the input's container.
-File I/O, text alignment, the 112-d hand-crafted features (unused by the model) and dataset bookkeeping stay out of scope.
+The 112-d hand-crafted features of the 516.79 Hz signal (data_utils.py:85-136) are csrc/emg_features.hip: mean removal, the two box
+filters and the per-frame statistics / 16-point spectra of every recording of a batch in one launch (data_utils.get_emg_features is the
+per-recording drop-in).  File I/O, text alignment and dataset bookkeeping stay out of scope.
 """
 import ctypes
 import math
@@ -192,6 +195,45 @@ def subsample_batch(signals, new_freq, old_freq):
     rc = _lib.lib().ss_linear_resample_batch(_lib.ptr(x), _lib.ptr(y), _lib.ptr(table), len(signals), C, float(old_freq), float(new_freq), int(oo[-1]), _lib.stream_of(x))
     _lib.check(rc, 'ss_linear_resample_batch')
     return [y[oo[u]:oo[u + 1]] for u in range(len(signals))]
+
+
+def feature_frames(n):
+    """Frames of librosa.util.frame(x, frame_length=16, hop_length=6) on n samples (data_utils.py:100); librosa raises below 16."""
+    return 0 if n < 16 else 1 + (n - 16) // 6
+
+
+def _packed_rows(signals):
+    """The (sum n_u, C) tensor the views in `signals` were cut from, back to back, or None if they were not (then a copy is needed)."""
+    t0 = signals[0]
+    C = int(t0.shape[1])
+    ptr, rows = t0.data_ptr(), 0
+    for t in signals:
+        if t.dtype != torch.float64 or not t.is_contiguous() or t.untyped_storage().data_ptr() != t0.untyped_storage().data_ptr() \
+                or int(t.shape[1]) != C or (t.numel() and t.data_ptr() != ptr + 8 * rows * C):
+            return None
+        rows += int(t.shape[0])
+    return t0.new_empty(0).set_(t0.untyped_storage(), t0.storage_offset(), (rows, C))
+
+
+def emg_features_batch(signals_516):
+    """data_utils.get_emg_features for a list of (n_u, C) f64 device tensors (the 516.79 Hz signals) in ONE launch -> list of (F_u, 14 C) f32
+    views of one packed buffer, F_u = 1 + (n_u - 16) // 6 (0 rows for n_u < 16, where the reference's librosa call raises).  The views
+    subsample_batch returns share one buffer and are read in place."""
+    dev = signals_516[0].device
+    C = int(signals_516[0].shape[1])
+    if any(t.dim() != 2 or int(t.shape[1]) != C for t in signals_516):
+        raise ValueError('signals: (n, C) tensors with one channel count')
+    lens = [int(t.shape[0]) for t in signals_516]
+    frames = [feature_frames(n) for n in lens]
+    x = _packed_rows(signals_516)
+    if x is None:
+        x = torch.cat([t.to(torch.float64) for t in signals_516], 0).contiguous()
+    io, oo = np.concatenate([[0], np.cumsum(lens)]), np.concatenate([[0], np.cumsum(frames)])
+    table = torch.from_numpy(np.stack([io[:-1], lens, oo[:-1], frames], 1).astype(np.int64)).to(dev, non_blocking=True)
+    y = torch.empty(int(oo[-1]), 14 * C, dtype=torch.float32, device=dev)
+    rc = _lib.lib().ss_emg_features_batch(_lib.ptr(x), _lib.ptr(y), _lib.ptr(table), len(signals_516), C, int(oo[-1]), _lib.stream_of(x))
+    _lib.check(rc, 'ss_emg_features_batch')
+    return [y] if len(signals_516) == 1 else [y[oo[u]:oo[u + 1]] for u in range(len(signals_516))]
 
 
 def remove_drift(signal, fs):

@@ -5,6 +5,7 @@
     dtw_align                        align.py:16-34 on one device matrix
     ctc_loss                         recognition_model.py:96-101
     stft_logmel                      data_utils.py:39-62
+    emg_features                     data_utils.py:85-136 (get_emg_features; no autograd: the reference's features are numpy)
     fused_adamw                      torch.optim.AdamW over the flat parameter arena (transduction_model.py:178,210)
 
 The package's own entry points (Model.forward, dtw_loss, ctc_loss, FusedAdamW.step, mel_spectrogram, align_from_distances) call these
@@ -228,6 +229,23 @@ def _(y, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, center)
     return y.new_empty(y.shape[0], num_mels, 1 + (Lp - n_fft) // hop_size)
 
 
+# ------------------------------------------------------------------------------------------------ emg_features
+@torch.library.custom_op('silent_speech::emg_features', mutates_args=())
+def emg_features(x: Tensor) -> Tensor:
+    """data_utils.py:85-136: (n, C) EMG at 516.79 Hz (n >= 16) -> (1 + (n - 16) // 6, 14 C) float32 features, f64 arithmetic."""
+    from .read_emg import emg_features_batch
+    if x.dim() != 2 or x.shape[0] < 16:
+        raise ValueError('emg_features: a (n >= 16, C) signal is expected')
+    return emg_features_batch([x.to(torch.float64).contiguous()])[0]
+
+
+@emg_features.register_fake
+def _(x):
+    if x.dim() != 2 or x.shape[0] < 16:
+        raise ValueError('emg_features: a (n >= 16, C) signal is expected')
+    return x.new_empty((1 + (x.shape[0] - 16) // 6, 14 * x.shape[1]), dtype=torch.float32)
+
+
 # ------------------------------------------------------------------------------------------------ fused_adamw
 @torch.library.custom_op('silent_speech::fused_adamw', mutates_args=('p', 'm', 'v'))
 def fused_adamw(p: Tensor, g: Tensor, m: Tensor, v: Tensor, n: int, lr: float, step: int, beta1: float, beta2: float, eps: float,
@@ -241,4 +259,4 @@ def _(p, g, m, v, n, lr, step, beta1, beta2, eps, weight_decay, grad_scale):
     return None
 
 
-OPS = ('model_forward', 'model_backward', 'dtw_loss', 'dtw_align', 'ctc_loss', 'stft_logmel', 'fused_adamw')
+OPS = ('model_forward', 'model_backward', 'dtw_loss', 'dtw_align', 'ctc_loss', 'stft_logmel', 'emg_features', 'fused_adamw')
