@@ -10,11 +10,16 @@ Workload (BASELINE config 2): full 768-d / 6-layer model, bf16 MFMA c
 reference-size batch per GPU (256 000 raw-sample budget => ~40 utterances, ~22 k frames, ~110 rows),
 25 % silent utterances.  Weak scaling: every rank gets its own batch of that size.
 
-  python bench.py --gpus N --steps K --warmup W        (N>1: launched under torch.distributed.run)
-Prints ONE JSON line on rank 0:
+  python bench.py --gpus N --steps K --warmup W [--full]        (N>1: launched under torch.distributed.run)
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line:
   value / ms_per_step   the K timed steps (barrier + synchronize on both sides, max over ranks)
   roofline              the kernel with the largest share of the step + a `kernels` list (MFMA- and HBM-bound ones):
                         HIP events around every launch on every 10th timed step (those steps run serially: no side stream)
+  rccl / allreduce      (N>1) the process group, communicators and gradient all-reduce of the timed steps
+--full also runs, after the timed loop, what the headline does not need (each with runs of its own; --no-same, --cpu-rows 0 and
+--no-legs leave parts out):
+  config.unprofiled     the rotating loop again and batch 0 on every step, both without per-launch events
+  n1_comparison         (N>1) the same command on one GPU of the node, run by rank 0 after the process group is gone
   cpu_baseline          the oracle (CPU restatement of the reference step) on >= 16 packed rows of the same batch, this node's cores
   parity                mel-L1 of the HIP model (bf16 and exact-f32 kernels) against the oracle on those rows, same weights
   dtw / mel             BASELINE configs[2] (64 and 256 x 1000^2 DTW, HIP vs the oracle's C twin on 1 core and on all cores) and the
@@ -462,7 +467,7 @@ def pipeline_leg(dev, n_utt=24):
 
 def n1_comparison(args, local_rank):
     """The same command on ONE GPU (this rank's), run by rank 0 after the process group is gone: the N = 1 figure the N-GPU line is read against,
-    measured on the same node in the same call.  No legs, no CPU baseline, no per-launch events."""
+    measured on the same node in the same call.  A plain run (no --full) without per-launch events."""
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'LOCAL_WORLD_SIZE', 'MASTER_PORT', 'GROUP_RANK', 'ROLE_RANK',
                                                            'TORCHELASTIC_RUN_ID', 'SS_BENCH_LAUNCHER', 'SS_BENCH_SCHEDULE')}
@@ -470,7 +475,7 @@ def n1_comparison(args, local_rank):
     if os.environ.get('SS_BENCH_BACKEND', 'nccl') != 'nccl':
         env.pop('HIP_VISIBLE_DEVICES', None)          # gloo ranks shared the GPUs that exist
     cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--steps', str(args.steps), '--warmup', str(args.warmup), '--dtype', args.dtype,
-           '--batches', str(args.batches), '--no-legs', '--no-profile', '--no-same', '--cpu-rows', '0']
+           '--batches', str(args.batches), '--no-profile']
     try:
         outp = subprocess.check_output(cmd, env=env, timeout=900).decode(errors='replace')
         d = json.loads([l for l in outp.splitlines() if l.startswith('{')][-1])
@@ -582,15 +587,17 @@ def main():
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--dtype', default='bf16', choices=['bf16', 'fp32', 'fp32x3'], help="fp32x3: f32 storage, every matmul product on three bf16 MFMAs (Model(f32_matmul='bf16x3'))")
-    ap.add_argument('--cpu-rows', type=int, default=16, help='packed rows of the batch given to the CPU baseline (0 = skip baseline and parity)')
+    ap.add_argument('--full', action='store_true', help='after the timed loop, also run what the headline does not need: the un-profiled comparison loops, the '
+                    'CPU baseline and parity, the DTW / mel / fp32-mode / CTC / eval / pipeline legs and (N > 1) the N = 1 comparison')
+    ap.add_argument('--cpu-rows', type=int, default=16, help='--full: packed rows of the batch given to the CPU baseline (0 = skip baseline and parity)')
     ap.add_argument('--cpu-steps', type=int, default=5)
     ap.add_argument('--cpu-warmup', type=int, default=3)
     ap.add_argument('--batches', type=int, default=4, help='distinct reference-size batches rotated through warm-up and the timed loop (1 = the same batch every step)')
-    ap.add_argument('--no-same', action='store_true', help='skip the same-batch comparison loop after the timed loop (profiling runs)')
+    ap.add_argument('--no-same', action='store_true', help='--full: skip the comparison loops after the timed loop (profiling runs)')
     ap.add_argument('--no-profile', action='store_true', help='no per-launch HIP events (roofline entry omitted)')
-    ap.add_argument('--no-legs', action='store_true', help='skip the DTW (configs[2]), mel, fp32-mode, CTC (configs[4]), eval and pipeline legs')
+    ap.add_argument('--no-legs', action='store_true', help='--full: skip the DTW (configs[2]), mel, fp32-mode, CTC (configs[4]), eval and pipeline legs')
     ap.add_argument('--scaling', default='weak', choices=['weak', 'strong'], help='weak: one reference-size batch per rank; strong: ONE such batch dealt over the ranks by length')
-    ap.add_argument('--cpu-full', type=int, default=1, help='also time the CPU baseline on the FULL batch (1 warm-up + 2 timed steps, ~1 min); 0 = sample only')
+    ap.add_argument('--cpu-full', type=int, default=1, help='--full: also time the CPU baseline on the FULL batch (2 warm-up + 5 timed steps, ~20 s each); 0 = sample only')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write the outputs of the last timed step to DIR/<name>.npy (rank 0)')
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
@@ -633,7 +640,7 @@ def main():
     model = Model(112, 80, 48, model_size=768, num_layers=6, dropout=0.2, compute_dtype=dt, f32_matmul='bf16x3' if args.dtype == 'fp32x3' else 'exact').to(dev)
     model.train()
     model.shift_rng = random.Random(rank)          # the shift augmentation draws (architecture.py:65) are seeded like everything else
-    init_sd = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
+    init_sd = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()} if args.full else None          # the --full legs start from these weights
     dp = DataParallel() if world > 1 else None
     if dp is not None:
         dp.attach(model)
@@ -740,7 +747,7 @@ def main():
     # without the side stream): the SAME loop rotating the batches, and the loop rounds 1-3 reported (batch 0 every step).
     same_ms = rot_ms = float('nan')
     n_same, rot_frames = 0, 0
-    if not args.no_same:
+    if args.full and not args.no_same:
         n_same = min(max(args.steps, len(batches)), 12)
 
         def loop(fn, n):
@@ -878,7 +885,7 @@ def main():
                                          'torch events on the launch stream) on every 10th (runs of <= 20 steps) / every (steps/2)-th timed step; those steps run without the side stream '
                                          '(exclusive durations); rocprofv3 counterpart: profiles/r06_serial_kernel_stats.txt',
                                'kernels': kernels[:16]}
-        if world == 1 and args.cpu_rows > 0:
+        if args.full and world == 1 and args.cpu_rows > 0:
             base, sub, ref_pred = cpu_baseline(batch_cpu, args.cpu_rows, args.cpu_warmup, args.cpu_steps, init_sd, dev)
             out['cpu_baseline'] = base
             out['parity'] = parity_entry(sub, ref_pred, init_sd, dev)
@@ -886,7 +893,7 @@ def main():
                 full, _, _ = cpu_baseline(batch_cpu, 10 ** 9, 2, 5, init_sd, dev, want_pred=False)        # sample (faster per frame: it fits the caches) rides along
                 full['bounded_sample'] = {k: base[k] for k in ('value', 'unit', 'cores', 'sample')}
                 out['cpu_baseline'] = full
-        if world == 1 and not args.no_legs:
+        if args.full and world == 1 and not args.no_legs:
             out['dtw'] = dtw_leg(dev)
             out['dtw']['saturating'] = {k: v for k, v in dtw_leg(dev, nb=256).items() if k in ('workload', 'hip_ms', 'matrices_per_s', 'roofline', 'bit_exact_vs_oracle')}
             out['mel'] = mel_leg(dev)
@@ -905,7 +912,7 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        if world > 1 and os.environ.get('SS_BENCH_N1', '1') != '0':
+        if args.full and world > 1 and os.environ.get('SS_BENCH_N1', '1') != '0':
             out['n1_comparison'] = n1_comparison(args, local_rank)
             if out['n1_comparison'].get('value'):
                 out['n1_comparison']['speedup_of_this_line'] = out['value'] / out['n1_comparison']['value']

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Round-end measurement on the GPU box: GPU tests, the default bench line, rocprofv3 kernel traces (overlapped and serial), the HBM
+# Round-end measurement on the GPU box: GPU tests, the full bench line (--full), rocprofv3 kernel traces (overlapped and serial), the HBM
 # traffic counters (FETCH_SIZE / WRITE_SIZE in separate --pmc passes, kernel trace only) and the SQ counters of the attention kernels.
 # Everything lands in gpurun_out/final/; copy what is to be judged into profiles/ (tracked).
 cd /tmp && export TMPDIR=/tmp
@@ -17,8 +17,8 @@ rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $O/pw -o pw -- python bench.py --st
 python tools/pmc_summary.py $(find $O/pf -name "*.db" | head -1) $(find $O/pw -name "*.db" | head -1) $O/pmc_traffic.json > $O/pmc_traffic.txt
 rm -rf $O/kt $O/ks $O/pf $O/pw
 cp $O/pmc_traffic.json profiles/r06_pmc_traffic.json            # the bench line's `traffic` fields come from THIS run's counters
-python bench.py > $O/bench.json.log 2>$O/bench.err
-for ss in 1 0; do SS_AMD_SIDE_STREAM=$ss python bench.py --no-profile --no-legs --cpu-rows 0 --steps 20 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('side_stream=$ss', d['ms_per_step'], d['config']['unprofiled'])"; done > $O/side_stream_ab.txt 2>&1
+python bench.py --full > $O/bench.json.log 2>$O/bench.err
+for ss in 1 0; do SS_AMD_SIDE_STREAM=$ss python bench.py --full --no-profile --no-legs --cpu-rows 0 --steps 20 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('side_stream=$ss', d['ms_per_step'], d['config']['unprofiled'])"; done > $O/side_stream_ab.txt 2>&1
 bash tools/attn_trace.sh > /dev/null 2>&1; cp gpurun_out/attn_trace/kernel_stats.txt $O/attention_kernel_stats.txt
 bash tools/attn_pmc.sh > /dev/null 2>&1; cp gpurun_out/attn_pmc/table.txt $O/attention_sq_counters.txt
 ./tools/bin/attn_bench > $O/attention_bench.txt 2>&1
