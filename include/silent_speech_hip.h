@@ -389,15 +389,16 @@ int ss_stft_logmel_fft(const float* y, const int64_t* offsets_dev, const int32_t
  * transposed copy [B][H*dp][Tp]; Dscratch [B][H][T] f32.  The embeddings receive no gradient
  * (transformer.py:214-218). */
 /* 1 if (dtype, T, dp, D) runs the per-tile attention kernels, which read the per-sequence transposed copies qkvT / dOT;
- * 0 if the LDS-resident kernels run (bf16, T <= 208, operands fit the 160 KB LDS): then qkvT and dOT may be NULL and the
- * producing GEMMs need not emit them. */
+ * 0 exactly when the transposed-score kernels run (family 2 below): then qkvT and dOT may be NULL and the producing GEMMs
+ * need not emit them. */
 int ss_relpos_attention_needs_transposed(int dtype, int T, int dp, int D); /* [host] */
-/* Which kernels (dtype, T, dp, D) runs: 0 = per-tile (qkvT / dOT needed), 1 = LDS-resident 16 x 16 tiles, 2 = transposed 32 x 32 score
- * tiles (bf16, T <= 224: csrc/attention_t.hip).  Family 2 reads the embeddings from a prepared table instead of E / ET:
+/* Which kernels (dtype, T, dp, D) runs: 0 = per-tile (qkvT / dOT needed), 2 = transposed 32 x 32 score tiles (bf16, T <= 224:
+ * csrc/attention_t.hip).  1 was the LDS-resident 16 x 16 family of rounds 1-4: retired, never returned, the number is not reused.
+ * Family 2 reads the embeddings from a prepared table instead of E / ET:
  * ss_relpos_attention_table_bytes() bytes, filled by ss_relpos_attention_prepare_tables from the f32 parameter
  * (transformer.py:172-176 `embeddings`, [H][2D-1][dh] contiguous; scale = 1/sqrt(d_qkv) as in the calls below) -- E / scale in
  * MFMA-fragment order, so that Q.E accumulates in the same accumulator as Q.K and the table streams from L2 as whole KiB.
- * `tab` may be NULL for families 0 and 1; E / ET / qkvT / dOT may be NULL for family 2. */
+ * `tab` may be NULL for family 0; E / ET / qkvT / dOT may be NULL for family 2. */
 int ss_relpos_attention_family(int dtype, int T, int dp, int D); /* [host] */
 int64_t ss_relpos_attention_table_bytes(int H, int dp, int D); /* [host] */
 int ss_relpos_attention_prepare_tables(const float* emb, void* tab, int H, int D, int dh, int dp, float scale, void* stream);
@@ -409,11 +410,11 @@ int ss_relpos_attention_backward(int dtype, const void* qkv, const void* qkvT, c
                                  int B, int H, int T, int Tp, int dp, int D, float scale, float dropout_p, uint64_t seed,
                                  uint32_t rng_stream, void* stream);
 
-/* The same with SAVED PROBABILITIES: the LDS-resident forward can leave its normalised probabilities (bf16, accumulator layout,
- * dropout decision in the sign bit; csrc/attention.hip "the P image") in `pimg`, ss_relpos_attention_saved_bytes() bytes; the
- * backward then reads them instead of recomputing both logit products, the skew, the exponentials and the dropout draws.
- * saved_bytes is 0 for shapes that run the per-tile kernels; pimg may be NULL in both calls (= the functions above), except that the
- * family-2 backward works ONLY from the saved probabilities (its forward may still run without pimg: inference). */
+/* The same with SAVED PROBABILITIES: the family-2 forward leaves its normalised probabilities (bf16, 32 x 32 blocks, dropout
+ * decision in the sign bit; csrc/attention_t.hip "the P image") in `pimg`, ss_relpos_attention_saved_bytes() bytes; its backward
+ * reads them instead of recomputing both logit products, the skew, the exponentials and the dropout draws, and works ONLY from them
+ * (the forward may still run without pimg: inference).  saved_bytes is 0 for shapes that run the per-tile kernels, which save
+ * nothing: there pimg must be NULL in both calls (= the functions above). */
 int64_t ss_relpos_attention_saved_bytes(int dtype, int B, int H, int T, int dp, int D); /* [host] */
 int ss_relpos_attention_forward_p(int dtype, const void* qkv, const void* qkvT, const void* E, const void* tab, void* out, float* lse, void* pimg,
                                   int B, int H, int T, int Tp, int dp, int D, float scale, float dropout_p, uint64_t seed,

@@ -69,7 +69,7 @@ def gemm_epilogue_mask(seed, stream, M, N, p):
 
 
 def attention_mask_tiled(seed, stream, B, H, T, p):
-    """Per-tile attention kernels (f32, or rows longer than the LDS-resident limit; csrc/attention.hip `attn_fwd_kernel`):
+    """Per-tile attention kernels (f32, or bf16 rows the transposed-score kernels do not take; csrc/attention.hip `attn_fwd_kernel`):
     probability (q, k) of pair bh <-> group ((bh*T + q/4)*T + k), slot q & 3.  -> bool (B, H, T, T)."""
     Tq = (T + 3) // 4 * 4
     bh = np.arange(B * H, dtype=np.uint64)[:, None, None]
@@ -77,25 +77,6 @@ def attention_mask_tiled(seed, stream, B, H, T, p):
     k = np.arange(T, dtype=np.uint64)[None, None, :]
     kp = keep4(seed, stream, (bh * np.uint64(T) + qg) * np.uint64(T) + k, p)          # (BH, Tq/4, T, 4)
     return np.ascontiguousarray(kp.transpose(0, 1, 3, 2)).reshape(B, H, Tq, T)[:, :, :T]
-
-
-def attention_mask_resident(seed, stream, B, H, T, p):
-    """LDS-resident attention kernels (bf16 rows of <= 208 frames; csrc/attention.hip `res_drop_key` / `res_drop_words` /
-    `res_drop_keep4`): the 4 query rows 4g..4g+3 of key column k draw 15-bit values from two words hashed from (pair, row group,
-    k); an entry is dropped iff its draw is below t15 = threshold >> 17.  -> bool (B, H, T, T)."""
-    with np.errstate(over='ignore'):
-        Tq = (T + 3) // 4 * 4
-        sd = U32(_seed_fold(seed, stream))
-        row = (np.arange(B * H, dtype=np.uint64)[:, None] * np.uint64(T) + np.arange(Tq // 4, dtype=np.uint64)[None, :]).astype(U32)
-        key = mix32((row * U32(0x9E3779B1)) ^ sd) + sd                                         # (BH, Tq/4)
-        k = np.arange(T, dtype=np.uint64).astype(U32)
-        a = (key[:, :, None] + U32(2) * k[None, None, :]) * U32(0x7feb352d)
-        a ^= a >> U32(15); a *= U32(0x846ca68b); a ^= a >> U32(16)
-        b = (a ^ U32(0x68E31DA4)) * U32(0x9E3779B1); b ^= b >> U32(15)
-        t15 = U32(dropout_threshold(p) >> 17)
-        kp = np.stack([(a & U32(0x7fff)) >= t15, ((a >> U32(16)) & U32(0x7fff)) >= t15,
-                       (b & U32(0x7fff)) >= t15, ((b >> U32(16)) & U32(0x7fff)) >= t15], 2)   # (BH, Tq/4, 4, T)
-        return kp.reshape(B, H, Tq, T)[:, :, :T]
 
 
 def attention_mask_transposed(seed, stream, B, H, T, p):
@@ -120,18 +101,23 @@ def attention_mask_transposed(seed, stream, B, H, T, p):
         return keep.reshape(B, H, T, Tk)[..., :T]
 
 
+def _attention_mask_fn(family):
+    if int(family) == 1:
+        raise ValueError('attention kernel family 1 (LDS-resident 16 x 16, rounds 1-4) is retired: ss_relpos_attention_family returns 0 or 2')
+    return {0: attention_mask_tiled, 2: attention_mask_transposed}[int(family)]
+
+
 def attention_mask(family, seed, stream, B, H, T, p):
-    """Keep mask of the attention probabilities for the kernel family ss_relpos_attention_family reports (0 per-tile, 1 LDS-resident
-    16 x 16, 2 transposed 32 x 32)."""
-    return (attention_mask_tiled, attention_mask_resident, attention_mask_transposed)[family](seed, stream, B, H, T, p)
+    """Keep mask of the attention probabilities for the kernel family ss_relpos_attention_family reports (0 per-tile, 2 transposed 32 x 32)."""
+    return _attention_mask_fn(family)(seed, stream, B, H, T, p)
 
 
-def layer_masks(seed, num_layers, B, T, d_model, n_head, ff, p, resident_attention):
+def layer_masks(seed, num_layers, B, T, d_model, n_head, ff, p, family):
     """Keep masks of one training forward as torch float tensors in the shapes `model_ref.encoder_layer` applies them:
-    [{'attn': (B,H,T,T), 'res1': (B,T,d), 'ffn': (B,T,ff), 'res2': (B,T,d)} for each layer]."""
+    [{'attn': (B,H,T,T), 'res1': (B,T,d), 'ffn': (B,T,ff), 'res2': (B,T,d)} for each layer].  family: the attention kernel
+    family number (0 / 2, see attention_mask)."""
     import torch
-    # resident_attention: bool of the earlier rounds (False = per-tile, True = LDS-resident 16 x 16) or the family number 0 / 1 / 2
-    att = (attention_mask_tiled, attention_mask_resident, attention_mask_transposed)[int(resident_attention)]
+    att = _attention_mask_fn(family)
     out = []
     for l in range(num_layers):
         out.append({

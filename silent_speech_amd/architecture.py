@@ -184,7 +184,7 @@ class Model(nn.Module):
 
     def attention_mask_family(self, T):
         """Which dropout-mask function the attention of a training forward on rows of T frames draws from (oracle/dropout_ref.attention_mask):
-        0 per-tile kernels, 1 LDS-resident 16 x 16 (A/B builds), 2 transposed-score kernels -- bf16 plans ask the library; an f32 plan runs the
+        0 per-tile kernels, 2 transposed-score kernels (1 is retired) -- bf16 plans ask the library; an f32 plan runs the
         per-tile kernels unless it is the parity-grade mode on hi / lo planes (f32_matmul='bf16x3'), whose attention is the transposed-score one."""
         import os
         from . import _lib

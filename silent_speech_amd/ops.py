@@ -334,7 +334,7 @@ def _attn_dt(qkv, f32_math):
 
 
 def relpos_attention_family(dtype, T, dp, D):
-    """0 = per-tile kernels (need qkvT / dOT), 1 = LDS-resident 16 x 16 tiles, 2 = transposed 32 x 32 score tiles (need the prepared tables)"""
+    """0 = per-tile kernels (need qkvT / dOT), 2 = transposed 32 x 32 score tiles (need the prepared tables)"""
     return int(_L().ss_relpos_attention_family(dtype if isinstance(dtype, int) else _lib.dtype_code(dtype), T, dp, D))
 
 

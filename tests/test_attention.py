@@ -1,7 +1,6 @@
 """Fused relative-position attention (forward + backward) vs the closed-form fp32 torch restatement
 (oracle/model_ref.relpos_logits, itself pinned to the reference's pad/view skew by golden vectors)."""
 import math
-import os
 
 import pytest
 import torch
@@ -61,7 +60,7 @@ def _run(dev, dt, B, H, T, dh, D, seed, tol_f, tol_b, p=0.0, f32_math='exact'):
     qkv_d, qkvT_d, E_d, ET_d = qkv.to(dev), qkvT.to(dev), Ed.to(dev), ETd.to(dev)
     scale = 1.0 / math.sqrt(dh)
     nsaved = ops.relpos_attention_saved_bytes(dt, B, H, T, dp, D)
-    saved = torch.empty(nsaved, dtype=torch.uint8, device=dev) if nsaved else None             # the probability image of the resident kernels
+    saved = torch.empty(nsaved, dtype=torch.uint8, device=dev) if nsaved else None             # the probability image of the transposed-score kernels
     ops.relpos_attention_forward(qkv_d, qkvT_d, E_d, out, lse, B, H, T, Tp, dp, D, scale, saved=saved, **kw)
     O = out.view(B, T, H, dp)[..., :dh].permute(0, 2, 1, 3)
     assert_close_robust(O, O_ref, tol_f, name='O', max_outlier_frac=0)
@@ -118,34 +117,6 @@ def test_attention_transposed_score_kernels(dev, case, p):
     _run(dev, torch.bfloat16, B=2, H=2 if is_emu(dev) else 8, T=T, dh=dh, D=D, seed=T + D, tol_f=2e-2, tol_b=3e-2, p=p)
 
 
-RES16_HIP = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'silent_speech_amd', 'lib', 'libsilent_speech_hip_res16.so')
-
-
-def _need_res16(dev, monkeypatch, T, dp, D):
-    """The LDS-resident 16 x 16 family (rounds 1-4) lives only in A/B builds of the library (-DSS_ATTN_RES16) since round 6: on the GPU the
-    test runs on build()'s libsilent_speech_hip_res16.so (the product sources with that family compiled in); the product library returns
-    after the test."""
-    monkeypatch.setenv('SS_ATTN_T', '0')
-    if not is_emu(dev):
-        from silent_speech_amd import _lib
-        monkeypatch.setattr(_lib, '_lib', _lib.lib())
-        _lib.load(RES16_HIP)
-    if ops.relpos_attention_family(torch.bfloat16, T, dp, D) != 1:
-        pytest.skip('the 16 x 16 resident attention kernels are compiled only into A/B builds (-DSS_ATTN_RES16)')
-
-
-
-@pytest.mark.parametrize('dt_old', [torch.bfloat16])
-def test_attention_resident_16x16_kernels_still_agree(dev, monkeypatch, dt_old):
-    """SS_ATTN_T=0 keeps the LDS-resident 16 x 16 kernels of rounds 1-4 reachable (A/B measurements): same function."""
-    dev_T, dev_dp, dev_D = (37, 32, 9) if is_emu(dev) else (200, 96, 100)
-    _need_res16(dev, monkeypatch, dev_T, dev_dp, dev_D)
-    if is_emu(dev):
-        _run(dev, dt_old, B=1, H=2, T=37, dh=8, D=9, seed=1, tol_f=2e-2, tol_b=3e-2, p=0.25)
-    else:
-        _run(dev, dt_old, B=2, H=8, T=200, dh=96, D=100, seed=1, tol_f=2e-2, tol_b=3e-2, p=0.2)
-
-
 @pytest.mark.parametrize('p', [0.0, 0.25])
 def test_attention_f32_storage_bf16x3_arithmetic(dev, p):
     """SS_F32X3 (the plan's parity-grade fast mode): f32 tensors, every product on three bf16 MFMAs.  Bars 10 x the exact-f32 ones
@@ -188,7 +159,7 @@ def test_attention_backward_uses_the_forward_dropout_mask(dev, dt):
     B, H, T, dh, D, p = 1, 2, 32, 32, 9, 0.3
     dp, Tp = 32, 32
     g = torch.Generator().manual_seed(21)
-    bf = dt == torch.bfloat16                                                           # bf16 rows of <= 208 frames: the LDS-resident kernels
+    bf = dt == torch.bfloat16                                                           # bf16 rows of <= 224 frames: the transposed-score kernels
     tolP, tolG = (2e-2, 3e-2) if bf else (2e-5, 5e-5)
     q, k = [(torch.randn(B, H, T, dh, generator=g) * 0.5).to(dt).float().requires_grad_(True) for _ in range(2)]
     v = torch.eye(T).expand(B, H, T, T).clone().requires_grad_(True)                    # dh == T
@@ -225,67 +196,8 @@ def test_attention_backward_uses_the_forward_dropout_mask(dev, dt):
         assert_close_robust(dq, q.grad, tolG, name='dQ', max_outlier_frac=0)
 
 
-@pytest.mark.parametrize('T,D,dh,p', [(40, 9, 32, 0.0), (72, 30, 64, 0.25), (200, 100, 96, 0.2)])
-def test_resident_forward_generations_agree(dev, monkeypatch, T, D, dh, p):
-    """The hand-scheduled resident forward (default) and the compiler-scheduled one (SS_ATTN_FWD2=0) implement the same function:
-    same log-sum-exp, same dropped set, outputs equal up to the bf16 rounding of the probabilities (normalised before vs after P~V)."""
-    if is_emu(dev) and T > 100:
-        pytest.skip('full-size rows: gpu tier')
-    B, H, dt = 2, 2, torch.bfloat16
-    dp, Tp = (dh + 31) // 32 * 32, (T + 7) // 8 * 8
-    _need_res16(dev, monkeypatch, T, dp, D)                   # the 16 x 16 resident kernels (rounds 1-4), kept behind this switch in A/B builds
-    g = torch.Generator().manual_seed(7)
-    qkv = (torch.randn(B * T, 3 * H * dp, generator=g) * 0.7).to(dt)
-    E = (torch.randn(H, 2 * D - 1, dp, generator=g) * dh ** -0.5).to(dt)
-    res = {}
-    for gen in ('0', '1'):
-        monkeypatch.setenv('SS_ATTN_FWD2', gen)
-        out = torch.zeros(B * T, H * dp, dtype=dt, device=dev); lse = torch.zeros(B, H, T, device=dev)
-        ops.relpos_attention_forward(qkv.to(dev), None, E.to(dev), out, lse, B, H, T, Tp, dp, D, 1.0 / math.sqrt(dh), p=p, seed=31, rng_stream=6)
-        res[gen] = (out.float().cpu(), lse.cpu())
-    assert_close_robust(res['1'][1], res['0'][1], 1e-5, name='lse', max_outlier_frac=0)
-    assert_close_robust(res['1'][0], res['0'][0], 2e-2, name='O', max_outlier_frac=0)
-
-
-@pytest.mark.parametrize('p,BH', [(0.0, (5, 2)), (0.2, (5, 2)), (0.2, (6, 2)), (0.0, (5, 1)), (0.0, (7, 1))])
-def test_persistent_per_head_schedule_equals_one_workgroup_per_pair(dev, monkeypatch, p, BH):
-    """More (sequence, head) pairs than CUs: the forward and the query-major backward run ONE persistent workgroup per CU that keeps its
-    head's embedding table in LDS and walks several sequences (whole ones, and a half of one of the last, partial round); SS_ATTN_PERSIST=0
-    is the old one-workgroup-per-pair launch.  Same arithmetic per pair: output, lse, the probability image and dqkv must be bit-identical."""
-    # emulator: 4 "CUs".  (5, 2): 2 workgroups per head, 2 whole sequences each + one split in halves; (6, 2): no partial round; (5, 1): 4 workgroups,
-    # two of them without a half; (7, 1): 3 left over of 4 -> not split (a second whole round for three workgroups).  GPU: the benchmarked launch.
-    # GPU: the same cases at the device's CU count -- (5, 2): the benchmarked launch (880 pairs); (6, 2): whole rounds only; (5, 1): a quarter round
-    # left over, split in halves; (7, 1): three quarters left over, not split.
-    cus = 4 if is_emu(dev) else torch.cuda.get_device_properties(dev).multi_processor_count
-    gpu_B = {(5, 2): 110, (6, 2): cus // 4, (5, 1): cus + cus // 4, (7, 1): cus + 3 * cus // 4}[BH]
-    B, H, T, dh, D = (BH[0], BH[1], 40, 32, 9) if is_emu(dev) else (gpu_B, 8 if BH[1] == 2 else 1, 200, 96, 100)
-    dt, dp, Tp = torch.bfloat16, (dh + 31) // 32 * 32, (T + 7) // 8 * 8
-    _need_res16(dev, monkeypatch, T, dp, D)                   # a schedule of the 16 x 16 resident kernels
-    g = torch.Generator().manual_seed(17)
-    qkv = (torch.randn(B * T, 3 * H * dp, generator=g) * 0.7).to(dt).to(dev)
-    E = (torch.randn(H, 2 * D - 1, dp, generator=g) * dh ** -0.5).to(dt)
-    MPt = (2 * D - 1 + 31) // 32 * 32
-    ET = torch.zeros(H, dp, MPt, dtype=dt); ET[:, :, :2 * D - 1] = E.transpose(1, 2)
-    E, ET = E.to(dev), ET.to(dev)
-    dO = torch.randn(B * T, H * dp, generator=g).to(dt).to(dev)
-    nsaved = ops.relpos_attention_saved_bytes(dt, B, H, T, dp, D)
-    assert nsaved > 0
-    res = {}
-    for mode in ('0', '1'):
-        monkeypatch.setenv('SS_ATTN_PERSIST', mode)
-        out = torch.zeros(B * T, H * dp, dtype=dt, device=dev); lse = torch.zeros(B, H, T, device=dev)
-        saved = torch.zeros(nsaved, dtype=torch.uint8, device=dev)
-        ops.relpos_attention_forward(qkv, None, E, out, lse, B, H, T, Tp, dp, D, 1.0 / math.sqrt(dh), p=p, seed=5, rng_stream=2, saved=saved)
-        dqkv = torch.zeros(B * T, 3 * H * dp, dtype=dt, device=dev); dsc = torch.empty(B, H, T, device=dev)
-        ops.relpos_attention_backward(qkv, None, E, ET, out, lse, dO, None, dsc, dqkv, B, H, T, Tp, dp, D, 1.0 / math.sqrt(dh), p=p, seed=5, rng_stream=2, saved=saved)
-        res[mode] = [t.cpu() for t in (out.view(torch.int16), lse, saved, dqkv.view(torch.int16))]
-    for a, b, name in zip(res['0'], res['1'], ('O', 'lse', 'image', 'dqkv')):
-        assert torch.equal(a, b), name
-    assert float(res['1'][0].float().abs().max()) > 0 and float(res['1'][3].float().abs().max()) > 0
-
-
 def test_transposed_copies_only_needed_by_the_per_tile_kernels(dev):
-    """ss_relpos_attention_needs_transposed: bf16 rows of <= 208 frames run the LDS-resident kernels (qkvT / dOT may be NULL);
+    """ss_relpos_attention_needs_transposed: bf16 rows of <= 224 frames run the transposed-score kernels (qkvT / dOT may be NULL);
     f32 and long sequences run the per-tile kernels, which refuse to start without them."""
     from silent_speech_amd import _lib
     L = _lib.lib()
@@ -297,7 +209,7 @@ def test_transposed_copies_only_needed_by_the_per_tile_kernels(dev):
     assert L.ss_relpos_attention_family(BF16, 200, 96, 100) == 2 and L.ss_relpos_attention_family(BF16, 225, 96, 100) == 0
     assert L.ss_relpos_attention_family(F32, 40, 32, 100) == 0
     assert L.ss_relpos_attention_needs_transposed(F32, 40, 32, 100) == 1
-    assert L.ss_relpos_attention_needs_transposed(BF16, 200, 128, 100) == 1          # operands do not fit the LDS
+    assert L.ss_relpos_attention_needs_transposed(BF16, 200, 128, 100) == 1          # d_head 128: not a transposed-score shape
     B, H, T, dp, D = 1, 2, 24, 32, 9
     for dt, ok in ((torch.bfloat16, True), (torch.float32, False)):
         qkv = torch.randn(B * T, 3 * H * dp).to(dt).to(dev)

@@ -51,8 +51,8 @@ def test_gemm_epilogue_mask(dev, dt):
 
 @pytest.mark.parametrize('dt', [torch.float32, torch.bfloat16])
 def test_attention_mask(dev, dt):
-    """V = I: the output IS the dropped-out probability matrix.  f32 runs the per-tile kernels, bf16 the LDS-resident ones; they
-    draw from different hashes (dropout_ref.attention_mask_tiled / _resident)."""
+    """V = I: the output IS the dropped-out probability matrix.  f32 runs the per-tile kernels, bf16 the transposed-score ones; they
+    draw from different hashes (dropout_ref.attention_mask_tiled / _transposed)."""
     B, H, T, dh, D, p = 2, 2, 32, 32, 9, 0.3
     dp, Tp = 32, 32
     seed, stream = 99, 4

@@ -39,14 +39,14 @@ int main(int argc, char** argv)
     CK(hipMemcpy(qkv, h.data(), nqkv * 2, hipMemcpyHostToDevice)); CK(hipMemcpy(E, hE.data(), nE * 2, hipMemcpyHostToDevice));
     CK(hipMemcpy(ET, hET.data(), nET * 2, hipMemcpyHostToDevice)); CK(hipMemcpy(dO, hdO.data(), nO * 2, hipMemcpyHostToDevice));
     if (ss_relpos_attention_needs_transposed(SS_BF16, T, dp, D)) { fprintf(stderr, "shape runs the per-tile kernels (needs transposed copies): not benchmarked here\n"); return 2; }
-    const int64_t nsaved = ss_relpos_attention_saved_bytes(SS_BF16, B, H, T, dp, D);          // 0 with SS_ATTN_SAVE_P=0: backward recomputes the probabilities
+    const int64_t nsaved = ss_relpos_attention_saved_bytes(SS_BF16, B, H, T, dp, D);          // the probability image the family-2 forward leaves for its backward
     void* pimg = nullptr; if (nsaved) CK(hipMalloc(&pimg, (size_t)nsaved));
     printf("saved probabilities: %.1f MB\n", nsaved / 1e6);
     hipStream_t st; CK(hipStreamCreate(&st));
     // family 2 (transposed 32 x 32 score tiles): the embedding table E / scale in fragment order, from the f32 embeddings [H][2D-1][dp]
     void* tab = nullptr;
     const int family = ss_relpos_attention_family(SS_BF16, T, dp, D);
-    printf("kernel family %d (0 per-tile, 1 LDS-resident 16x16, 2 transposed 32x32)\n", family);
+    printf("kernel family %d (0 per-tile, 2 transposed 32x32)\n", family);
     if (family == 2) {
         std::vector<float> hf(nE); for (size_t i = 0; i < nE; ++i) { uint32_t u = (uint32_t)hE[i] << 16; memcpy(&hf[i], &u, 4); }
         float* embf; CK(hipMalloc(&embf, nE * 4)); CK(hipMemcpy(embf, hf.data(), nE * 4, hipMemcpyHostToDevice));
