@@ -30,9 +30,9 @@ extern "C" {
 const char* ss_last_error(void);
 /* Library/ABI version and the GPU architecture the kernels were compiled for ("gfx950"). */
 /* Bumped whenever a struct layout or an entry-point signature changes (3: ss_gemm_epilogue column-statistics fields, the plan /
- * attention-image / LayerNorm-workspace entry points, ss_dtw_cumulative; 4: ss_loss_index_tables; 5: gate recomputation arguments of ss_bn_backward_sums / ss_bn_backward_apply; 7: ss_split_planes / ss_gemm_planes, ss_dw_job.flags, up to 24 jobs per grouped launch; 8: ss_stft_logmel_fft, the rejected-frame counter behind the matrix of ss_phoneme_confusion; 9: planes_hi / planes_lo / planes_only of ss_gemm_epilogue, dropout groups of the GEMM epilogue are row-major; 10: ss_emg_features_batch).  Bindings must compare it with SS_ABI_VERSION at load time: a stale
+ * attention-image / LayerNorm-workspace entry points, ss_dtw_cumulative; 4: ss_loss_index_tables; 5: gate recomputation arguments of ss_bn_backward_sums / ss_bn_backward_apply; 7: ss_split_planes / ss_gemm_planes, ss_dw_job.flags, up to 24 jobs per grouped launch; 8: ss_stft_logmel_fft, the rejected-frame counter behind the matrix of ss_phoneme_confusion; 9: planes_hi / planes_lo / planes_only of ss_gemm_epilogue, dropout groups of the GEMM epilogue are row-major; 10: ss_emg_features_batch; 11: the ss_voc_* vocoder entry points).  Bindings must compare it with SS_ABI_VERSION at load time: a stale
  * library paired with newer headers would otherwise read garbage struct fields instead of failing. */
-#define SS_ABI_VERSION 10
+#define SS_ABI_VERSION 11
 int ss_abi_version(void);
 const char* ss_target_arch(void);
 
@@ -516,6 +516,48 @@ int ss_plan_profile(ss_plan* plan, int enable);                                 
 int ss_plan_profile_read(ss_plan* plan, ss_profile_row* rows, int max_rows);      /* [host] */
 /* counters[i][0] += delta for n <= 16 device int64 counters (BatchNorm num_batches_tracked, architecture.py:19,21,25) in one launch */
 int ss_counters_add(int n, int64_t** counters /* [host] array of device pointers */, int64_t delta, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * HiFi-GAN generator (vocoder.py:16-36: Generator(hparams) of the hifi_gan submodule, called on mel.T[None]): predicted mels -> audio
+ * for a ragged batch of utterances packed back to back, replacing the cuDNN / MIOpen conv1d, conv_transpose1d, leaky_relu and tanh calls of
+ * that module.  Every activation is f32, TIME-MAJOR: a row is one time step with its channels contiguous (torch's x[0, :, t]), utterances
+ * back to back.  table_dev: int64 [n_utt][2] = {first mel frame, mel frames} per utterance, ONE table for every layer: a buffer at `scale`
+ * samples per mel frame (the product of the upsampling rates applied so far) holds utterance u in rows [first * scale, (first + frames) *
+ * scale).  max_frames = the longest utterance's mel frames (sizes the launch).  Every utterance has its own zero padding at both ends, by
+ * predication: rows of a neighbour are never read as padding and no padded copy is made.  x3 != 0: operands split into hi + lo bf16
+ * planes, three MFMAs per product, f32 accumulate (16-17 significant bits per operand); x3 == 0: one bf16 MFMA per product.
+ *
+ * Weight blob of one layer (built once at load time by the caller; co_pad = c_out rounded up to 16, ci_pad = c_in rounded up to 32,
+ * padding zero):   f32 bias[co_pad] | bf16 hi[slots][co_pad][ci_pad] | bf16 lo[slots][co_pad][ci_pad],   hi = bf16(w), lo = bf16(w - hi).
+ *   convolution (torch weight [c_out][c_in][k]):            slots = k,                       slot j         = weight[:, :, j]
+ *   transposed convolution (torch weight [c_in][c_out][k]): slots = stride * ceil(k / stride), slot r * ceil(k / stride) + m = weight[:, :, r + m * stride].T
+ *                                                           (zero where r + m * stride >= k): the taps of output phase r, polyphase form. */
+int64_t ss_voc_blob_bytes(int slots, int c_out, int c_in);          /* [host] bytes of such a blob; -1 on bad sizes */
+/* [host] bytes of the generator's activation workspace for total_frames packed mel frames: FOUR equal buffers (this value / 4 each,
+ * 256-byte aligned) as wide as the widest layer (conv_pre output at c_initial channels, stage i at c_initial >> (i + 1) channels and
+ * rates[0] * .. * rates[i] rows per frame): the stage input, the two ResBlock temporaries and the multi-receptive-field sum. */
+int64_t ss_voc_workspace_bytes(int64_t total_frames, int c_initial, const int* rates /* [host] */, int n_ups);
+/* [host] 1 if the kernels take the shape.  kind 0: ss_voc_conv1d (c_in % 8 == 0, c_out % 4 == 0, k odd, (k - 1) * dilation <= 128);
+ * kind 1: ss_voc_conv_transpose1d (same channel rules, k >= stride, k - stride even); kind 2: ss_voc_tail (c_in <= 64, c_out == 1, k odd <= 15). */
+int ss_voc_supported(int c_in, int c_out, int k, int dilation_or_stride, int kind);
+/* Fused dilated convolution, one launch (F.leaky_relu + Conv1d(c_in, c_out, k, dilation=d, padding=(k - 1) d / 2) [+ the ResBlock's
+ * `xt + x`] [+ the generator's `xs += resblock(x)` and `/ num_kernels`] of hifi_gan's ResBlock1/2.forward and Generator.forward; conv_pre with slope 1):
+ *     v = bias[co] + sum_tap sum_ci W[tap][co][ci] * lrelu_slope(x[t + (tap - (k - 1) / 2) d][ci])  + (residual ? residual[t][co] : 0)
+ *     out[t][co] = ((accumulate ? out[t][co] : 0) + v) * out_scale
+ * x rows have c_in floats, residual / out rows c_out; out must not be x; residual may be out. */
+int ss_voc_conv1d(const float* x, const void* blob, const float* residual, float* out, const int64_t* table_dev, int n_utt,
+                  int64_t max_frames, int scale, int c_in, int c_out, int k, int dilation, float slope, int accumulate,
+                  float out_scale, int x3, void* stream);
+/* F.leaky_relu + ConvTranspose1d(c_in, c_out, k, stride, padding=(k - stride) / 2) of Generator.forward, polyphase: out row t (out has
+ * scale * stride rows per mel frame) = bias + sum over taps j = (t + p) mod stride, + stride, .. of W[:, :, j] . lrelu(x[(t + p - j) / stride]),
+ * p = (k - stride) / 2; no zero-stuffed intermediate exists. */
+int ss_voc_conv_transpose1d(const float* x, const void* blob, float* out, const int64_t* table_dev, int n_utt, int64_t max_frames,
+                            int scale, int c_in, int c_out, int k, int stride, float slope, int x3, void* stream);
+/* The generator's last three calls (F.leaky_relu at torch's default slope 0.01, conv_post = Conv1d(c_in, 1, k, padding (k - 1) / 2),
+ * torch.tanh) in one pass, exact f32: out[first * scale + t] = tanh(w[k c_in] + sum_j sum_c w[j c_in + c] lrelu(x[t + j - (k - 1) / 2][c])).
+ * w: f32 [k][c_in] followed by the bias. */
+int ss_voc_tail(const float* x, const float* w, float* out, const int64_t* table_dev, int n_utt, int64_t max_frames, int scale,
+                int c_in, int k, float slope, void* stream);
 
 #ifdef __cplusplus
 }

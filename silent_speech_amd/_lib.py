@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.environ.get('SS_AMD_LIBRARY') or os.path.join(_HERE, 'lib', 'libsilent_speech_hip.so')      # override: A/B runs of two builds on one box
 
 SS_F32, SS_BF16, SS_F64, SS_F32X3 = 0, 1, 2, 3
-ABI_VERSION = 10         # include/silent_speech_hip.h: SS_ABI_VERSION (struct layouts / signatures this binding was written against)
+ABI_VERSION = 11         # include/silent_speech_hip.h: SS_ABI_VERSION (struct layouts / signatures this binding was written against)
 OP_KC, OP_OC = 0, 1
 
 
@@ -106,6 +106,9 @@ SIGNATURES = {
     'ss_iir_filtfilt_batch': [_P, _P, _P, _I, _I, _I, _P, _P, _L, _P],
     'ss_linear_resample_batch': [_P, _P, _P, _I, _I, ctypes.c_double, ctypes.c_double, _L, _P],
     'ss_emg_features_batch': [_P, _P, _P, _I, _I, _L, _P],
+    'ss_voc_conv1d': [_P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _I, _I, _F, _I, _F, _I, _P],
+    'ss_voc_conv_transpose1d': [_P, _P, _P, _P, _I, _L, _I, _I, _I, _I, _I, _F, _I, _P],
+    'ss_voc_tail': [_P, _P, _P, _P, _I, _L, _I, _I, _I, _F, _P],
     'ss_stft_magnitude': [_P, _L, _I, _P, _L, _I, _P],
     'ss_stft_logmel_fft': [_P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P, _L, _L, _L, _P],
 }
@@ -141,6 +144,9 @@ _HOST_FUNCS = {'ss_dtw_workspace_bytes': ([_I, _I, _LP, _LP, _LP], ctypes.c_int6
                'ss_relpos_attention_x3_saved_bytes': ([_I, _I, _I, _I, _I], ctypes.c_int64),
                'ss_relpos_attention_x3_table_bytes': ([_I, _I, _I], ctypes.c_int64),
                'ss_relpos_attention_saved_bytes': ([_I, _I, _I, _I, _I, _I], ctypes.c_int64),
+               'ss_voc_blob_bytes': ([_I, _I, _I], ctypes.c_int64),
+               'ss_voc_workspace_bytes': ([_L, _I, ctypes.POINTER(ctypes.c_int), _I], ctypes.c_int64),
+               'ss_voc_supported': ([_I, _I, _I, _I, _I], ctypes.c_int),
                'ss_layernorm_backward_scratch_floats': ([_I, _I], ctypes.c_int64)}
 _RESTYPES = {'ss_last_error': ctypes.c_char_p, 'ss_target_arch': ctypes.c_char_p, 'ss_abi_version': ctypes.c_int}
 

@@ -464,3 +464,72 @@ class PermuteBatch(object):
         nbytes = sum(j.d0 * j.d1 * j.d2 * ((4 if j.in_dtype == 0 else 2) + (4 if j.out_dtype == 0 else 2)) for j in self.jobs)
         timed('permute3d_batch (weight re-layout)', 0, nbytes,
               lambda: _lib.check(_L().ss_permute3d_batch(_p(jobs), _p(jb), total, all_f32, _s(jobs)), 'ss_permute3d_batch'))
+
+
+# ------------------------------------------------------------------------------------------------ HiFi-GAN generator (vocoder.hip)
+def voc_blob_bytes(slots, c_out, c_in):
+    n = int(_lib.lib().ss_voc_blob_bytes(int(slots), int(c_out), int(c_in)))
+    if n < 0:
+        raise ValueError('ss_voc_blob_bytes: bad sizes (slots %d, c_out %d, c_in %d)' % (slots, c_out, c_in))
+    return n
+
+
+def voc_workspace_bytes(total_frames, c_initial, rates):
+    arr = (ctypes.c_int * max(len(rates), 1))(*[int(r) for r in rates])
+    n = int(_lib.lib().ss_voc_workspace_bytes(int(total_frames), int(c_initial), arr, len(rates)))
+    if n < 0:
+        raise ValueError('ss_voc_workspace_bytes: bad sizes')
+    return n
+
+
+def voc_supported(c_in, c_out, k, dilation_or_stride, kind):
+    """kind 0: voc_conv1d, 1: voc_conv_transpose1d, 2: voc_tail."""
+    return bool(_lib.lib().ss_voc_supported(int(c_in), int(c_out), int(k), int(dilation_or_stride), int(kind)))
+
+
+def _voc_check(x, out, table, n_utt, rows_in, rows_out, c_in, c_out):
+    for t in (x, out):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError('vocoder kernels take contiguous float32 activations')
+    if table.dtype != torch.int64 or not table.is_contiguous() or table.numel() < 2 * n_utt:
+        raise ValueError('vocoder kernels take an int64 [n_utt][2] table of (first frame, frames)')
+    if x.numel() < rows_in * c_in or out.numel() < rows_out * c_out:
+        raise ValueError('vocoder kernel: a buffer is smaller than the packed rows it has to hold')
+
+
+def voc_conv1d(x, blob, out, table, n_utt, total_frames, max_frames, scale, c_in, c_out, k, dilation, slope, residual=None,
+               accumulate=False, out_scale=1.0, x3=True):
+    """include/silent_speech_hip.h: ss_voc_conv1d.  x / out: packed time-major rows of total_frames * scale steps."""
+    rows = total_frames * scale
+    _voc_check(x, out, table, n_utt, rows, rows, c_in, c_out)
+    if residual is not None and (residual.dtype != torch.float32 or residual.numel() < rows * c_out):
+        raise ValueError('voc_conv1d: residual must be float32 and cover the output rows')
+    if blob.numel() * blob.element_size() < voc_blob_bytes(k, c_out, c_in):
+        raise ValueError('voc_conv1d: weight blob too small')
+    rc = _lib.lib().ss_voc_conv1d(_lib.ptr(x), _lib.ptr(blob), _lib.ptr(residual), _lib.ptr(out), _lib.ptr(table), int(n_utt), int(max_frames),
+                                  int(scale), int(c_in), int(c_out), int(k), int(dilation), float(slope), int(bool(accumulate)), float(out_scale),
+                                  int(bool(x3)), _lib.stream_of(out))
+    _lib.check(rc, 'ss_voc_conv1d')
+    return out
+
+
+def voc_conv_transpose1d(x, blob, out, table, n_utt, total_frames, max_frames, scale, c_in, c_out, k, stride, slope, x3=True):
+    """include/silent_speech_hip.h: ss_voc_conv_transpose1d.  x: total_frames * scale rows, out: total_frames * scale * stride rows."""
+    _voc_check(x, out, table, n_utt, total_frames * scale, total_frames * scale * stride, c_in, c_out)
+    if blob.numel() * blob.element_size() < voc_blob_bytes(stride * (-(-k // stride)), c_out, c_in):
+        raise ValueError('voc_conv_transpose1d: weight blob too small')
+    rc = _lib.lib().ss_voc_conv_transpose1d(_lib.ptr(x), _lib.ptr(blob), _lib.ptr(out), _lib.ptr(table), int(n_utt), int(max_frames), int(scale),
+                                            int(c_in), int(c_out), int(k), int(stride), float(slope), int(bool(x3)), _lib.stream_of(out))
+    _lib.check(rc, 'ss_voc_conv_transpose1d')
+    return out
+
+
+def voc_tail(x, w, out, table, n_utt, total_frames, max_frames, scale, c_in, k, slope=0.01):
+    """include/silent_speech_hip.h: ss_voc_tail.  w: float32 [k * c_in + 1] (the last one is the bias); out: total_frames * scale samples."""
+    _voc_check(x, out, table, n_utt, total_frames * scale, total_frames * scale, c_in, 1)
+    if w.dtype != torch.float32 or w.numel() < k * c_in + 1:
+        raise ValueError('voc_tail: w must hold k * c_in + 1 floats')
+    rc = _lib.lib().ss_voc_tail(_lib.ptr(x), _lib.ptr(w), _lib.ptr(out), _lib.ptr(table), int(n_utt), int(max_frames), int(scale), int(c_in), int(k),
+                                float(slope), _lib.stream_of(out))
+    _lib.check(rc, 'ss_voc_tail')
+    return out

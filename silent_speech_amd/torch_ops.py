@@ -7,6 +7,7 @@
     stft_logmel                      data_utils.py:39-62
     emg_features                     data_utils.py:85-136 (get_emg_features; no autograd: the reference's features are numpy)
     fused_adamw                      torch.optim.AdamW over the flat parameter arena (transduction_model.py:178,210)
+    vocoder_conv1d / vocoder_conv_transpose1d / vocoder_tail      the three kernel families of the HiFi-GAN generator (vocoder.py:16-36), inference only
 
 The package's own entry points (Model.forward, dtw_loss, ctc_loss, FusedAdamW.step, mel_spectrogram, align_from_distances) call these
 ops, so the drop-in surface reaches the kernels THROUGH the dispatcher; every op has a fake (meta) implementation for shape inference
@@ -15,7 +16,7 @@ tensors and plain scalars only; per-model state (bound plan, weight copies) is l
 Emulator builds (tests) run the same registrations on CPU tensors.
 """
 import weakref
-from typing import Tuple
+from typing import Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -259,4 +260,61 @@ def _(p, g, m, v, n, lr, step, beta1, beta2, eps, weight_decay, grad_scale):
     return None
 
 
-OPS = ('model_forward', 'model_backward', 'dtw_loss', 'dtw_align', 'ctc_loss', 'stft_logmel', 'emg_features', 'fused_adamw')
+# ------------------------------------------------------------------------------------------------ HiFi-GAN generator (inference only: no autograd)
+# One op per kernel family over ONE utterance of L time steps, time-major (L, C) float32 -- the packed, multi-utterance form is what
+# vocoder.Vocoder drives through ops.voc_* (one table for all ~80 launches of a call).  `blob` is the layer's weight blob (vocoder.conv_blob /
+# vocoder.conv_transpose_blob / vocoder.tail_weights).
+def _one_utterance(x):
+    if x.dim() != 2 or x.dtype != torch.float32:
+        raise ValueError('a time-major (L, C) float32 tensor is expected')
+    return torch.tensor([[0, x.shape[0]]], dtype=torch.int64, device=x.device), x.contiguous()
+
+
+@torch.library.custom_op('silent_speech::vocoder_conv1d', mutates_args=())
+def vocoder_conv1d(x: Tensor, blob: Tensor, c_out: int, k: int, dilation: int, slope: float, residual: Optional[Tensor], x3: bool) -> Tensor:
+    """conv1d(leaky_relu(x, slope), W, b, dilation=dilation, padding=(k - 1) * dilation // 2) [+ residual], (L, c_in) -> (L, c_out)."""
+    table, x = _one_utterance(x)
+    L, c_in = x.shape
+    out = x.new_empty((L, c_out))
+    if residual is not None:
+        if residual.shape != out.shape or residual.dtype != torch.float32:
+            raise ValueError('vocoder_conv1d: residual must be (L, c_out) float32')
+        residual = residual.contiguous()
+    return ops.voc_conv1d(x, blob, out, table, 1, L, L, 1, c_in, c_out, k, dilation, slope, residual=residual, x3=x3)
+
+
+@vocoder_conv1d.register_fake
+def _(x, blob, c_out, k, dilation, slope, residual, x3):
+    return x.new_empty((x.shape[0], c_out))
+
+
+@torch.library.custom_op('silent_speech::vocoder_conv_transpose1d', mutates_args=())
+def vocoder_conv_transpose1d(x: Tensor, blob: Tensor, c_out: int, k: int, stride: int, slope: float, x3: bool) -> Tensor:
+    """conv_transpose1d(leaky_relu(x, slope), W, b, stride=stride, padding=(k - stride) // 2), (L, c_in) -> (L * stride, c_out)."""
+    table, x = _one_utterance(x)
+    L, c_in = x.shape
+    out = x.new_empty((L * stride, c_out))
+    return ops.voc_conv_transpose1d(x, blob, out, table, 1, L, L, 1, c_in, c_out, k, stride, slope, x3=x3)
+
+
+@vocoder_conv_transpose1d.register_fake
+def _(x, blob, c_out, k, stride, slope, x3):
+    return x.new_empty((x.shape[0] * stride, c_out))
+
+
+@torch.library.custom_op('silent_speech::vocoder_tail', mutates_args=())
+def vocoder_tail(x: Tensor, w: Tensor, k: int, slope: float) -> Tensor:
+    """tanh(conv1d(leaky_relu(x, slope), W (1, c_in, k), b, padding=(k - 1) // 2)), (L, c_in) -> (L,)."""
+    table, x = _one_utterance(x)
+    L, c_in = x.shape
+    out = x.new_empty((L,))
+    return ops.voc_tail(x, w, out, table, 1, L, L, 1, c_in, k, slope)
+
+
+@vocoder_tail.register_fake
+def _(x, w, k, slope):
+    return x.new_empty((x.shape[0],))
+
+
+OPS = ('model_forward', 'model_backward', 'dtw_loss', 'dtw_align', 'ctc_loss', 'stft_logmel', 'emg_features', 'fused_adamw',
+       'vocoder_conv1d', 'vocoder_conv_transpose1d', 'vocoder_tail')

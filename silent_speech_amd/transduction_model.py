@@ -3,6 +3,7 @@
     dtw_loss(predictions, phoneme_predictions, example, phoneme_eval=False, phoneme_confusion=None)   (:98-157)
     test(model, testset, device)                                                                       (:33-55)
     train_model(trainset, devset, device, save_sound_outputs=True)                                     (:159-227)
+    save_output(model, datapoint, filename, device, audio_normalizer, vocoder)                         (:57-73)
 
 dtw_loss keeps everything on the GPU: cost matrices are produced directly in the DTW kernel's strip
 layout, DTW + backtrace run on device, and loss/gradient touch only the aligned pairs -- no D2H copy
@@ -10,6 +11,7 @@ of a T1 x T2 matrix and no per-utterance synchronisation (the reference blocks o
 """
 import logging
 import os
+import wave
 
 import numpy as np
 import torch
@@ -248,7 +250,7 @@ class EnsembleModel(torch.nn.Module):
 def predict_utterance(model, datapoint, device):
     """The model half of save_output (transduction_model.py:57-66): eval-mode forward of ONE whole utterance
     (un-chunked: T is the utterance length, the banded attention kernel skips everything beyond +-99 frames).
-    Returns the (T, n_mel) prediction on the device; vocoding (:68-72) is outside the hot path."""
+    Returns the (T, n_mel) prediction on the device; save_output vocodes it (:68-72)."""
     was_training = model.training
     model.eval()
     with torch.no_grad():
@@ -258,6 +260,36 @@ def predict_utterance(model, datapoint, device):
         pred, _ = model(X, X_raw, sess)
     model.train(was_training)
     return pred.squeeze(0)
+
+
+def _inverse_on_device(audio_normalizer, y):
+    """FeatureNormalizer.inverse (data_utils.py:155-156) without the reference's round trip through the host (:67): the normaliser's
+    numpy statistics are broadcast on the device the prediction already lives on."""
+    if hasattr(audio_normalizer, 'feature_means') and hasattr(audio_normalizer, 'feature_stddevs'):
+        std = torch.as_tensor(np.asarray(audio_normalizer.feature_stddevs), dtype=torch.float32).to(y.device)
+        mean = torch.as_tensor(np.asarray(audio_normalizer.feature_means), dtype=torch.float32).to(y.device)
+        return y * std + mean
+    return audio_normalizer.inverse(y)
+
+
+def write_wav(filename, audio, sampling_rate=22050):
+    """1-D float audio in [-1, 1] -> mono 16-bit PCM wav (sample = rint(clip(x, -1, 1) * 32767)); the reference's sf.write(filename, audio, 22050)."""
+    pcm = np.rint(np.clip(np.asarray(audio, dtype=np.float64), -1.0, 1.0) * 32767.0).astype('<i2')
+    with wave.open(filename, 'wb') as f:
+        f.setnchannels(1)
+        f.setsampwidth(2)
+        f.setframerate(int(sampling_rate))
+        f.writeframes(pcm.tobytes())
+
+
+def save_output(model, datapoint, filename, device, audio_normalizer, vocoder):
+    """transduction_model.py:57-73: EMG -> model -> de-normalised mel -> HiFi-GAN -> wav, everything up to the samples on the device
+    (vocoder: a silent_speech_amd.vocoder.Vocoder).  Unlike the reference (:73 leaves the model in train mode) the model is returned to
+    the mode it was in."""
+    y = predict_utterance(model, datapoint, device)
+    with torch.no_grad():
+        audio = vocoder(_inverse_on_device(audio_normalizer, y))
+    write_wav(filename, audio.cpu().numpy())
 
 
 def get_aligned_prediction(model, datapoint, device, audio_normalizer):
