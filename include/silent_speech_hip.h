@@ -30,9 +30,9 @@ extern "C" {
 const char* ss_last_error(void);
 /* Library/ABI version and the GPU architecture the kernels were compiled for ("gfx950"). */
 /* Bumped whenever a struct layout or an entry-point signature changes (3: ss_gemm_epilogue column-statistics fields, the plan /
- * attention-image / LayerNorm-workspace entry points, ss_dtw_cumulative; 4: ss_loss_index_tables; 5: gate recomputation arguments of ss_bn_backward_sums / ss_bn_backward_apply; 7: ss_split_planes / ss_gemm_planes, ss_dw_job.flags, up to 24 jobs per grouped launch; 8: ss_stft_logmel_fft, the rejected-frame counter behind the matrix of ss_phoneme_confusion; 9: planes_hi / planes_lo / planes_only of ss_gemm_epilogue, dropout groups of the GEMM epilogue are row-major; 10: ss_emg_features_batch; 11: the ss_voc_* vocoder entry points).  Bindings must compare it with SS_ABI_VERSION at load time: a stale
+ * attention-image / LayerNorm-workspace entry points, ss_dtw_cumulative; 4: ss_loss_index_tables; 5: gate recomputation arguments of ss_bn_backward_sums / ss_bn_backward_apply; 7: ss_split_planes / ss_gemm_planes, ss_dw_job.flags, up to 24 jobs per grouped launch; 8: ss_stft_logmel_fft, the rejected-frame counter behind the matrix of ss_phoneme_confusion; 9: planes_hi / planes_lo / planes_only of ss_gemm_epilogue, dropout groups of the GEMM epilogue are row-major; 10: ss_emg_features_batch; 11: the ss_voc_* vocoder entry points; 12: the ragged-batch inference entry points ss_bn_apply_ragged, ss_relpos_attention_forward_ragged, ss_plan_forward_ragged).  Bindings must compare it with SS_ABI_VERSION at load time: a stale
  * library paired with newer headers would otherwise read garbage struct fields instead of failing. */
-#define SS_ABI_VERSION 11
+#define SS_ABI_VERSION 12
 int ss_abi_version(void);
 const char* ss_target_arch(void);
 
@@ -237,6 +237,13 @@ int ss_bn_finalize_shift(const float* sums, const float* shift, double n_total, 
 int ss_bn_apply(int dtype, const void* xa, const float* mean_a, const float* invstd_a, const float* gamma_a, const float* beta_a, int pad_xa,
                 const void* xb, const float* mean_b, const float* invstd_b, const float* gamma_b, const float* beta_b, int pad_xb,
                 void* y, int pad_y, int B, int T, int C, int relu, void* stream);
+/* The same for a RAGGED batch in equal slots (inference; ss_plan_forward_ragged): sequence b owns rows t < lens_dev[b] * len_mul of its slot of T
+ * rows (lens in model frames; len_mul = 4, 2, 1 for the three ResBlocks), rows behind that are stored as 0 -- the select that already writes the
+ * pad rows, with a per-sequence bound -- so that the right tap of the next k = 3 convolution reads the zero padding an utterance has when it runs
+ * alone (architecture.py:18,20 padding=1) and not its slot's filler.  The filler rows of the inputs are never converted, whatever they hold. */
+int ss_bn_apply_ragged(int dtype, const void* xa, const float* mean_a, const float* invstd_a, const float* gamma_a, const float* beta_a, int pad_xa,
+                       const void* xb, const float* mean_b, const float* invstd_b, const float* gamma_b, const float* beta_b, int pad_xb,
+                       void* y, int pad_y, int B, int T, int C, int relu, const int32_t* lens_dev, int len_mul, void* stream);
 /* autograd backward of the above (transduction_model.py:209), again in two phases:
  * sums[3][C] = { sum g, sum g*xhat_a, sum g*xhat_b } with g = dy*1[y>0]; dgamma/dbeta are ACCUMULATED (+=);
  * apply: dx = gamma*invstd*(g - sums0/n - xhat*sums{1,2}/n).
@@ -424,6 +431,15 @@ int ss_relpos_attention_backward_p(int dtype, const void* qkv, const void* qkvT,
                                    int B, int H, int T, int Tp, int dp, int D, float scale, float dropout_p, uint64_t seed,
                                    uint32_t rng_stream, void* stream);
 
+/* Inference forward of a RAGGED batch in equal slots (per-tile kernels, any T; dtype SS_F32, SS_F32X3 or SS_BF16): sequence b holds
+ * lens_dev[b] <= T frames at the start of its slot of T rows (qkv, out) / Tp columns (qkvT).  The slot length only addresses the operands;
+ * the sequence length bounds everything else: queries of sequence b see keys k < lens_dev[b] (inside the band rule above), V^T fragments and
+ * K rows behind it are zeroed by select, and 16-row query tiles that start at or behind it leave before their first load (the launch covers
+ * the slots; lengths stay on the device).  Rows >= lens_dev[b] of `out` are not written.  No dropout, no lse: there is no backward.
+ * Rows t < lens_dev[b] equal what ss_relpos_attention_forward gives for sequence b alone (B = 1, T = lens_dev[b]). */
+int ss_relpos_attention_forward_ragged(int dtype, const void* qkv, const void* qkvT, const void* E, void* out, const int32_t* lens_dev,
+                                       int B, int H, int T, int Tp, int dp, int D, float scale, void* stream);
+
 /* The parity-grade mode of the attention (round 6): f32 operands as hi / lo bf16 planes (ss_split_planes), every product of the kernels above
  * on three bf16 MFMAs (a_lo.b_hi + a_hi.b_lo + a_hi.b_hi, f32 accumulate) -- the transposed-score kernels' formulation, so bf16 rows of up to
  * 224 frames, d_head <= 96 (ss_relpos_attention_x3_supported; other shapes keep SS_F32X3 of the entry points above).  qkv / dO arrive as
@@ -505,6 +521,15 @@ int64_t ss_plan_workspace_bytes(ss_plan* plan, int B, int T0, int training); /* 
  * shift_r == 0).  ctx_out [host, ss_plan_ctx_bytes()] must be kept, with the workspace, until ss_plan_backward has run. */
 int ss_plan_forward(ss_plan* plan, const float* x_raw, float* shifted_scratch, void* workspace, int64_t workspace_bytes, int B, int T0,
                     int training, int shift_r, float dropout_p, uint64_t seed, float* head, void* ctx_out, void* stream);
+/* Eval-mode forward of a RAGGED batch of whole utterances (evaluate.py's output loop, transduction_model.py:57-66,75-85, recognition_model.py:37-43
+ * run one utterance per call): utterance b holds lens_dev[b] >= 1 model frames (8 lens[b] raw samples) at the start of slot b of x_raw (B, T0, 8),
+ * zero filled behind them; head rows [b * T0/8, b * T0/8 + lens[b]) equal ss_plan_forward(B = 1, training = 0) of that utterance alone, the other
+ * rows of a slot are unspecified.  Same plan, with ss_bn_apply_ragged for every BatchNorm apply and ss_relpos_attention_forward_ragged for the
+ * attention (always the per-tile kernels: the QKV GEMM always writes qkvT, planes are never adopted for attention).  No context is kept: there is
+ * no backward.  lens_host [host, may be NULL]: the same lengths, read only by the profile rows (attention work counted from the real lengths). */
+int64_t ss_plan_workspace_bytes_ragged(ss_plan* plan, int B, int T0); /* [host] */
+int ss_plan_forward_ragged(ss_plan* plan, const float* x_raw, const int32_t* lens_dev, const int32_t* lens_host, void* workspace, int64_t workspace_bytes,
+                           int B, int T0, float* head, void* stream);
 /* Accumulates (+=) the gradient of every bound parameter; dhead [B*T0/8][n_head_cols] f32.  The weight-gradient GEMMs, bias column sums
  * and gradient un-layouts run on side_stream (may equal stream or be NULL), joined into `stream` before the call returns. */
 int ss_plan_backward(ss_plan* plan, void* ctx, const float* dhead, void* stream, void* side_stream);

@@ -2,6 +2,8 @@
 
     Model(num_features, num_outs, num_aux_outs=None)          architecture.py:43
     .forward(x_feat, x_raw, session_ids) -> pred | (pred, aux)  architecture.py:61-84
+    .forward_utterances(raws) -> preds | (preds, auxs)         the eval-mode forward of a list of WHOLE utterances of different lengths, one native
+                                                              call for all of them, each result what forward gives for that utterance alone
 
 Same parameter names / shapes / initialisation (so `state_dict()` round-trips with reference
 checkpoints), same train()/eval() semantics (random 0-7 sample shift augmentation drawn from Python's
@@ -17,6 +19,7 @@ at 1.8 x the speed; the fastest mode inside north_star's 1e-4 mel-L1).
 """
 import random
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -83,6 +86,7 @@ class Model(nn.Module):
         self._seed_base, self._step = 0x5EED, 0
         self.shift_rng = random                           # architecture.py:65 draws r = random.randrange(8)
         self._anchor = None
+        self._ragged_lens_host = None                     # host copy of the lengths of the forward_utterances call in flight (profile rows)
         self._flat = None
         self._cache = {}
 
@@ -228,3 +232,49 @@ class Model(nn.Module):
         if self.has_aux_out:
             return pred, head[:, n_out:n_out + self.num_aux_outs].view(B, T, self.num_aux_outs)
         return pred
+
+    def forward_utterances(self, raws):
+        """Eval-mode forward of a list of whole utterances, raw EMG (8 T_b, 8) float32 each, as ONE ragged batch: B equal slots of T_max = max T_b
+        frames, zero filled, through one native plan call (torch.ops.silent_speech.model_forward_ragged).  Returns (preds, auxs) -- just preds
+        without an aux head --, lists of (T_b, .) views in input order; every one equals forward() on that utterance alone (batch of 1), which is
+        what the reference's inference loops compute (transduction_model.py:57-66,75-85, recognition_model.py:37-43).  Inference only: the result
+        carries no autograd graph, and training mode (batch statistics over filler rows, dropout, the shift) is refused."""
+        from . import staging
+        if self.training:
+            raise RuntimeError('forward_utterances is an eval-mode forward (running BatchNorm statistics, no dropout, no shift): call model.eval() first')
+        raws = list(raws)
+        if not raws:
+            return ([], []) if self.has_aux_out else []
+        for r in raws:
+            if r.dim() != 2 or r.shape[1] != 8:
+                raise ValueError('every utterance must be (time, 8)')
+            if r.dtype != torch.float32:
+                raise TypeError('raw EMG must be float32')
+            if r.shape[0] % 8 != 0 or r.shape[0] == 0:
+                raise ValueError('raw EMG length %d must be a multiple of 8 (three stride-2 convolutions)' % r.shape[0])
+        dev = self.w_out.weight.device
+        lens = np.asarray([r.shape[0] // 8 for r in raws], dtype=np.int32)
+        B, T = len(raws), int(lens.max())
+        if all(r.device.type == 'cpu' for r in raws):
+            # host utterances: the slot tensor is laid out in the pinned staging buffer and crosses PCIe with the length table in ONE copy
+            slots = np.zeros((B, 8 * T, 8), dtype=np.float32)
+            for b, r in enumerate(raws):
+                slots[b, :r.shape[0]] = r.numpy()
+            x, lens_dev = staging.upload([slots, lens], dev)
+        else:
+            lens_dev, = staging.upload([lens], dev)
+            x = torch.zeros(B, 8 * T, 8, dtype=torch.float32, device=dev)
+            for b, r in enumerate(raws):
+                x[b, :r.shape[0]].copy_(r, non_blocking=True)
+        self._ragged_lens_host = lens
+        try:
+            with torch.no_grad():
+                head = torch.ops.silent_speech.model_forward_ragged(x, lens_dev, torch_ops.model_handle(self))
+        finally:
+            self._ragged_lens_host = None
+        n_out = self.num_outs
+        head = head.view(B, T, -1)
+        preds = [head[b, :int(n), :n_out] for b, n in enumerate(lens)]
+        if self.has_aux_out:
+            return preds, [head[b, :int(n), n_out:n_out + self.num_aux_outs] for b, n in enumerate(lens)]
+        return preds

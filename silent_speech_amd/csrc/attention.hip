@@ -47,6 +47,7 @@ struct AttnP {
     int B, H, T, Tp, dp, D, MPt, gx;
     float scale;
     unsigned drop_thresh; float drop_scale; unsigned long long seed; unsigned stream;
+    const int* lens;          // ragged inference forward: frames of each sequence inside its slot of T rows (NULL elsewhere)
 };
 
 constexpr int NB_MAX = 16;      // 16-key blocks per query tile: ceil((31 + 16 + 2*99)/16)
@@ -275,6 +276,100 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnP p)
 #pragma unroll
             for (int reg = 0; reg < 4; ++reg) { const int q = q0 + g * 4 + reg; if (q < Tn) stf(O + (long long)q * (H * dp) + n * 16 + c, o[n][reg]); }
     }
+}
+
+// =========================================================================== forward, ragged batch (inference)
+// attn_fwd_kernel for a batch of whole utterances in equal slots.  That kernel hard-wires the sequence stride and the sequence length to the same Tn;
+// here the slot length Tn = p.T only ADDRESSES Q, K, V^T and O, and the sequence's own length Tl = p.lens[b] bounds the key blocks, the k < Tl test of
+// the logits, the zeroing of the V^T fragments and the row clamp of the K loads, so that rows t < Tl come out as they do for the sequence alone.
+// A query tile that starts at or behind Tl leaves before its first load (waves are independent: nothing below is a workgroup barrier).  No dropout
+// draw, no lse store: there is no backward.  (A kernel of its own and not a template flag of attn_fwd_kernel: folding the two changed the instruction
+// schedule of the training-path kernel.)
+template <class MT, int DPK>
+__global__ __launch_bounds__(256) void attn_fwd_ragged_kernel(AttnP p)
+{
+    typedef typename StorageOf<MT>::type T;
+    __shared__ __attribute__((aligned(16))) T ptile[4][16][PT_LD];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
+    int bxi, h, b; attn_block_coord(p.gx, p.H, bxi, h, b);
+    const int q0 = (bxi * 4 + w) * 16;
+    const int Tn = p.T, D = p.D, dp = p.dp, H = p.H;
+    const long long ldq = 3LL * H * dp;
+    const T* Q = (const T*)p.qkv + (long long)b * Tn * ldq + h * dp;
+    const T* K = Q + H * dp;
+    const T* VT = (const T*)p.qkvT + ((long long)b * 3 * H * dp + 2 * H * dp + h * dp) * p.Tp;
+    const T* E = (const T*)p.E + (long long)h * (2 * D - 1) * dp;
+    int Tl = p.lens[b]; Tl = Tl < 0 ? 0 : (Tl > Tn ? Tn : Tl);
+    if (q0 >= Tl) return;
+
+    int kstart = q0 - (D - 1); kstart = kstart < 0 ? 0 : kstart; kstart &= ~31;
+    int kend = q0 + 16 + (D - 1); kend = kend > Tl ? Tl : kend;
+    const int nb = (kend - kstart + 15) / 16;
+    const int m_org = kstart - q0 - 15 + (D - 1);
+
+    Frag<MT> qf[DPK];
+    { int qr = q0 + c; qr = qr < Tl ? qr : Tl - 1; row_frags<T, DPK>(qf, Q + (long long)qr * ldq, true, lane); }
+
+    float lg[NB_MAX][4];
+    f32x4 rprev;
+    { Frag<MT> ef[DPK]; row_frags_nb<T, DPK>(ef, E, dp, m_org + c, 2 * D - 1, lane); rprev = dot_frags<T, DPK>(qf, ef); }
+    // All NB_MAX key blocks are computed unconditionally and branch-free (blocks beyond the band are masked to -inf):
+    // with no control flow between them the scheduler overlaps the fragment loads of later blocks with the MFMAs,
+    // shuffles and softmax prologue of earlier ones.
+#pragma unroll
+    for (int j = 0; j < NB_MAX; ++j) {
+        const int k0 = kstart + 16 * j;
+        Frag<MT> kf[DPK], ef[DPK];
+        row_frags_nb<T, DPK>(kf, K, ldq, k0 + c, Tl, lane);
+        row_frags_nb<T, DPK>(ef, E, dp, m_org + 16 * (j + 1) + c, 2 * D - 1, lane);
+        const f32x4 s = dot_frags<T, DPK>(qf, kf);
+        const f32x4 rn = dot_frags<T, DPK>(qf, ef);
+        float pos[4];
+        skew_gather(rprev, rn, lane, pos);
+        finish_logits(s, pos, q0, k0, lane, j < nb ? Tl : 0, D, p.scale, lg[j]);
+        rprev = rn;
+    }
+    // ---- softmax over the band (row = g*4+reg lives on the 16 lanes of group g)
+    float mx[4], sm[4];
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+        float m = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < NB_MAX; ++j) m = fmaxf(m, lg[j][reg]);
+        mx[reg] = group16_max(m);
+        float s = 0.f;
+#pragma unroll
+        for (int j = 0; j < NB_MAX; ++j) { const float e = lg[j][reg] == -INFINITY ? 0.f : expf(lg[j][reg] - mx[reg]); lg[j][reg] = e; s += e; }
+        sm[reg] = group16_sum(s);
+    }
+    // ---- P (normalised) -> LDS in A-operand order (all NB_MAX blocks: zeros beyond the band)
+#pragma unroll
+    for (int j = 0; j < NB_MAX; ++j) {
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            const float pv = sm[reg] > 0.f ? lg[j][reg] / sm[reg] : 0.f;
+            stf(&ptile[w][g * 4 + reg][16 * j + c], pv);
+        }
+    }
+    wave_lds_sync();
+    // ---- O = P V  (B operand straight from the transposed copy of V); unconditional over the whole tile width
+    f32x4 o[2 * DPK];
+#pragma unroll
+    for (int n = 0; n < 2 * DPK; ++n) { f32x4 z = {0.f, 0.f, 0.f, 0.f}; o[n] = z; }
+#pragma unroll
+    for (int kc = 0; kc < NB_MAX / 2; ++kc) {
+        Frag<MT> pa; frag_load(pa, &ptile[w][c][kc * 32 + g * 8]);
+#pragma unroll
+        for (int n = 0; n < 2 * DPK; ++n) {
+            Frag<MT> vb; time_frag_nb(vb, VT + (long long)(n * 16 + c) * p.Tp, kstart + kc * 32 + g * 8, Tl, p.Tp);
+            o[n] = mma32(pa, vb, o[n]);
+        }
+    }
+    T* O = (T*)p.out + (long long)b * Tn * (H * dp) + h * dp;
+#pragma unroll
+    for (int n = 0; n < 2 * DPK; ++n)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) { const int q = q0 + g * 4 + reg; if (q < Tl) stf(O + (long long)q * (H * dp) + n * 16 + c, o[n][reg]); }
 }
 
 // =========================================================================== backward helpers
@@ -623,6 +718,22 @@ extern "C" int ss_relpos_attention_forward_p(int dtype, const void* qkv, const v
     dim3 grid(p.gx * H * B);
     SS_ATTN_DISPATCH(attn_fwd_kernel, grid, 256, 0);
     SS_LAUNCH_CHECK("ss_relpos_attention_forward");
+    return 0;
+}
+
+// Inference forward of a ragged batch in equal slots: always the per-tile kernels (the slot stride and the sequence length are separate there).
+// The launch covers every tile of every slot in the XCD-aware order of attn_block_coord; tiles behind a sequence's end exit before their first load.
+extern "C" int ss_relpos_attention_forward_ragged(int dtype, const void* qkv, const void* qkvT, const void* E, void* out, const int32_t* lens_dev,
+                                                  int B, int H, int T, int Tp, int dp, int D, float scale, void* stream)
+{
+    if (attn_check("ss_relpos_attention_forward_ragged", dtype, B, H, T, Tp, dp, D, 0.f)) return 1;
+    SS_CHECK(qkv && qkvT && E && out && lens_dev, "ss_relpos_attention_forward_ragged: null pointer");
+    AttnP p; attn_fill(p, B, H, T, Tp, dp, D, scale, 0.f, 0, 0);
+    p.qkv = qkv; p.qkvT = qkvT; p.E = E; p.out = out; p.lens = (const int*)lens_dev;
+    p.gx = ((T + 15) / 16 + 3) / 4;
+    dim3 grid(p.gx * H * B);
+    SS_ATTN_DISPATCH(attn_fwd_ragged_kernel, grid, 256, 0);
+    SS_LAUNCH_CHECK("ss_relpos_attention_forward_ragged");
     return 0;
 }
 

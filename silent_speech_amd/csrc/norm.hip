@@ -212,12 +212,19 @@ struct RowWalk {
     __device__ __forceinline__ void next() { ro += rstep; b += db; tp += dtp; if (tp >= TP) { tp -= TP; ++b; } }
 };
 
-template <class T>
+// RAGGED (inference on a batch of whole utterances in equal slots, ss_bn_apply_ragged): sequence b owns rows t < lens[b] * len_mul of its slot; the rows
+// behind them are stored as zeros like the halo rows -- by select, their inputs are never loaded
+template <class T, bool RAGGED = false>
 __global__ void bn_apply_kernel(const T* __restrict__ xa, Seq sa, const float* __restrict__ mean_a, const float* __restrict__ invstd_a, const float* __restrict__ gamma_a, const float* __restrict__ beta_a,
                                 const T* __restrict__ xb, Seq sb, const float* __restrict__ mean_b, const float* __restrict__ invstd_b, const float* __restrict__ gamma_b, const float* __restrict__ beta_b,
-                                T* __restrict__ y, Seq sy, int B, int C, int relu)
+                                T* __restrict__ y, Seq sy, int B, int C, int relu, const int* __restrict__ lens, int len_mul)
 {
     const int CV = C >> 3, TT = sy.T;
+    auto rows_of = [&](unsigned b) -> int {          // valid rows of sequence b
+        if (!RAGGED) return TT;
+        const int n = lens[b] * len_mul;
+        return n < 0 ? 0 : (n < TT ? n : TT);
+    };
     const unsigned TP = (unsigned)(TT + 2 * sy.pad), rows_out = (unsigned)B * TP, step32 = gridDim.x * blockDim.x;     // the host checks rows_out * CV < 2^31
     if (step32 % (unsigned)CV == 0) {
         RowWalk w(blockIdx.x * blockDim.x + threadIdx.x, step32, (unsigned)CV, TP);
@@ -241,7 +248,7 @@ __global__ void bn_apply_kernel(const T* __restrict__ xa, Seq sa, const float* _
         Raw nv = RawVec8<T>::zero(), nu = RawVec8<T>::zero();
         auto fetch = [&](unsigned b, unsigned tp) {
             const int t = (int)tp - sy.pad;
-            if (t >= 0 && t < TT) {
+            if (t >= 0 && t < rows_of(b)) {
                 nv = RawVec8<T>::load(xa + sa.at((int)b, t) * C + w.cx * 8);
                 if (xb) nu = RawVec8<T>::load(xb + sb.at((int)b, t) * C + w.cx * 8);
             }
@@ -258,7 +265,7 @@ __global__ void bn_apply_kernel(const T* __restrict__ xa, Seq sa, const float* _
             float o[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) o[e] = 0.f;                 // zero halo rows
-            if (t >= 0 && t < TT) {
+            if (t >= 0 && t < rows_of(w.b)) {
                 float v[8], u[8];
                 RawVec8<T>::unpack(cv, v);
                 if (xb) RawVec8<T>::unpack(cu, u);
@@ -282,7 +289,7 @@ __global__ void bn_apply_kernel(const T* __restrict__ xa, Seq sa, const float* _
         const unsigned ro = i / (unsigned)CV; const int cx = (int)(i - ro * (unsigned)CV);
         const unsigned bq = ro / TP; const int b = (int)bq, tp = (int)(ro - bq * TP), t = tp - sy.pad;
         float o[8];
-        if (t < 0 || t >= TT) {
+        if (t < 0 || t >= rows_of(bq)) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) o[e] = 0.f;             // zero halo rows
         } else {
@@ -332,9 +339,25 @@ extern "C" int ss_bn_apply(int dtype, const void* xa, const float* mean_a, const
     Seq sa = {T, pad_xa}, sb = {T, pad_xb}, sy = {T, pad_y};
     const long long total = (long long)B * (T + 2 * pad_y) * (C / 8);
     SS_CHECK(total < (1LL << 31) - (1LL << 22), "ss_bn_apply: tensor too large for 32-bit chunk indices");
-    if (dtype == SS_BF16) SS_LAUNCH(bn_apply_kernel<bf16_t>, ew_grid(total, 256, C / 8), dim3(256), 0, stream, (const bf16_t*)xa, sa, mean_a, invstd_a, gamma_a, beta_a, (const bf16_t*)xb, sb, mean_b, invstd_b, gamma_b, beta_b, (bf16_t*)y, sy, B, C, relu);
-    else SS_LAUNCH(bn_apply_kernel<float>, ew_grid(total, 256, C / 8), dim3(256), 0, stream, (const float*)xa, sa, mean_a, invstd_a, gamma_a, beta_a, (const float*)xb, sb, mean_b, invstd_b, gamma_b, beta_b, (float*)y, sy, B, C, relu);
+    if (dtype == SS_BF16) SS_LAUNCH(bn_apply_kernel<bf16_t>, ew_grid(total, 256, C / 8), dim3(256), 0, stream, (const bf16_t*)xa, sa, mean_a, invstd_a, gamma_a, beta_a, (const bf16_t*)xb, sb, mean_b, invstd_b, gamma_b, beta_b, (bf16_t*)y, sy, B, C, relu, (const int*)nullptr, 1);
+    else SS_LAUNCH(bn_apply_kernel<float>, ew_grid(total, 256, C / 8), dim3(256), 0, stream, (const float*)xa, sa, mean_a, invstd_a, gamma_a, beta_a, (const float*)xb, sb, mean_b, invstd_b, gamma_b, beta_b, (float*)y, sy, B, C, relu, (const int*)nullptr, 1);
     SS_LAUNCH_CHECK("ss_bn_apply");
+    return 0;
+}
+
+extern "C" int ss_bn_apply_ragged(int dtype, const void* xa, const float* mean_a, const float* invstd_a, const float* gamma_a, const float* beta_a, int pad_xa,
+                                  const void* xb, const float* mean_b, const float* invstd_b, const float* gamma_b, const float* beta_b, int pad_xb,
+                                  void* y, int pad_y, int B, int T, int C, int relu, const int32_t* lens_dev, int len_mul, void* stream)
+{
+    SS_CHECK(xa && mean_a && invstd_a && gamma_a && beta_a && y && lens_dev, "ss_bn_apply_ragged: null pointer");
+    SS_CHECK(!xb || (mean_b && invstd_b && gamma_b && beta_b), "ss_bn_apply_ragged: second branch incomplete");
+    SS_CHECK(C % 8 == 0 && C > 0 && B > 0 && T > 0 && len_mul >= 1, "ss_bn_apply_ragged: bad shape B=%d T=%d C=%d len_mul=%d", B, T, C, len_mul);
+    Seq sa = {T, pad_xa}, sb = {T, pad_xb}, sy = {T, pad_y};
+    const long long total = (long long)B * (T + 2 * pad_y) * (C / 8);
+    SS_CHECK(total < (1LL << 31) - (1LL << 22), "ss_bn_apply_ragged: tensor too large for 32-bit chunk indices");
+    if (dtype == SS_BF16) SS_LAUNCH(SS_KERNEL(bn_apply_kernel<bf16_t, true>), ew_grid(total, 256, C / 8), dim3(256), 0, stream, (const bf16_t*)xa, sa, mean_a, invstd_a, gamma_a, beta_a, (const bf16_t*)xb, sb, mean_b, invstd_b, gamma_b, beta_b, (bf16_t*)y, sy, B, C, relu, (const int*)lens_dev, len_mul);
+    else SS_LAUNCH(SS_KERNEL(bn_apply_kernel<float, true>), ew_grid(total, 256, C / 8), dim3(256), 0, stream, (const float*)xa, sa, mean_a, invstd_a, gamma_a, beta_a, (const float*)xb, sb, mean_b, invstd_b, gamma_b, beta_b, (float*)y, sy, B, C, relu, (const int*)lens_dev, len_mul);
+    SS_LAUNCH_CHECK("ss_bn_apply_ragged");
     return 0;
 }
 

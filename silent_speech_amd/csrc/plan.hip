@@ -326,7 +326,9 @@ struct Plan {
         }
     };
 
-    int forward(Exec& X, const float* x_raw, float* shifted, int B, int T0, int training, int shift_r, float p_drop, unsigned long long seed, float* head, Ctx* c);
+    // ragged: a batch of whole utterances in equal slots (eval only); lens = their model frames on the device (null in the sizing pass), lens_host (optional) feeds the profile rows
+    int forward(Exec& X, const float* x_raw, float* shifted, int B, int T0, int training, int shift_r, float p_drop, unsigned long long seed, float* head, Ctx* c,
+                bool ragged = false, const int32_t* lens = nullptr, const int32_t* lens_host = nullptr);
     int backward(Exec& X, Ctx* c, const float* dhead);
 };
 
@@ -336,8 +338,14 @@ struct Plan {
 // 2 dp flops per pair and product -- 3 products forward (QK, QE, PV), 5 backward (dP, dS K, dR E, P^T dO, dS^T Q)
 static double band_pairs(int T, int D) { double n = 0; for (int q = 0; q < T; ++q) { const int lo = q - (D - 1) < 0 ? 0 : q - (D - 1), hi = q + (D - 1) > T - 1 ? T - 1 : q + (D - 1); n += hi - lo + 1; } return n; }
 
-int Plan::forward(Exec& X, const float* x_raw, float* shifted, int B, int T0, int training, int shift_r, float p_drop, unsigned long long seed, float* head, Ctx* c)
+int Plan::forward(Exec& X, const float* x_raw, float* shifted, int B, int T0, int training, int shift_r, float p_drop, unsigned long long seed, float* head, Ctx* c,
+                  bool ragged, const int32_t* lens, const int32_t* lens_host)
 {
+    // Ragged batch (ss_plan_forward_ragged): utterance b fills the first lens[b] model frames of slot b.  The layout, the row maps, the GEMMs, LayerNorm and the
+    // heads are those of a dense batch; two kernels take the lengths: every BatchNorm apply stores zeros behind an utterance's end (valid rows per slot:
+    // 4, 2, 1 x lens[b] in the three blocks), so that the right tap of each k = 3 convolution reads the zero padding the utterance has when it runs alone, and the
+    // attention bounds its keys by lens[b].  Everything else works row by row: the filler rows of a slot hold finite values nobody reads into a valid row.
+    SS_CHECK(!ragged || (!training && (X.dry || lens)), "ragged batches are eval-mode only and need their lengths");
     const int dt = D.dtype, d = D.d_model; const size_t es = esz();
     const int Cin0 = 8;
     SS_CHECK(T0 % 8 == 0, "raw EMG length %d must be a multiple of 8 (three stride-2 convolutions)", T0);
@@ -377,14 +385,18 @@ int Plan::forward(Exec& X, const float* x_raw, float* shifted, int B, int T0, in
         if (training && hook && f1 && fr == f1 + 2 * d && O == d && !X.dry) nred = hook(hook_user, f1, 4 * O, (double)B * Tout, stream);
         L_(bn_stats(X, c1, B, Tout, O, s.scratch, w.bn1, training, &s.m1, &s.i1, f1, nred));
         void* h1 = X.alloc((size_t)B * (Tout + 2) * O * es);
-        if (!X.dry) L_(timed(X, "bn_apply", 0, (double)B * Tout * O * es * 2, stream, [&] { return ss_bn_apply(dt, c1, s.m1, s.i1, w.bn1.gamma, w.bn1.beta, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, h1, 1, B, Tout, O, 1, stream); }));
+        if (!X.dry) L_(timed(X, "bn_apply", 0, (double)B * Tout * O * es * 2, stream, [&] {
+            if (ragged) return ss_bn_apply_ragged(dt, c1, s.m1, s.i1, w.bn1.gamma, w.bn1.beta, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, h1, 1, B, Tout, O, 1, lens, 4 >> i, stream);
+            return ss_bn_apply(dt, c1, s.m1, s.i1, w.bn1.gamma, w.bn1.beta, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, h1, 1, B, Tout, O, 1, stream); }));
         void* c2 = X.alloc((size_t)rows * O * es);
         float* f2 = conv_gemm(X, h1, w.w2f, c2, rows, O, 3 * O, RM(O, Tout, (long long)(Tout + 2) * O), RM(3 * O), w.b2, w.bn2, slot ? slot + 4 * d : nullptr, &rc); L_(rc);
         L_(bn_stats(X, c2, B, Tout, O, s.scratch, w.bn2, training, &s.m2, &s.i2, f2));
         L_(bn_stats(X, cr, B, Tout, O, s.scratch, w.bnr, training, &s.mr, &s.ir, fr, nred));
         const int pad_y = i == 2 ? 0 : 1;
         void* y = X.alloc((size_t)B * (Tout + 2 * pad_y) * O * es);
-        if (!X.dry) L_(timed(X, "bn_apply", 0, (double)B * Tout * O * es * 3, stream, [&] { return ss_bn_apply(dt, c2, s.m2, s.i2, w.bn2.gamma, w.bn2.beta, 0, cr, s.mr, s.ir, w.bnr.gamma, w.bnr.beta, 0, y, pad_y, B, Tout, O, 1, stream); }));
+        if (!X.dry) L_(timed(X, "bn_apply", 0, (double)B * Tout * O * es * 3, stream, [&] {
+            if (ragged) return ss_bn_apply_ragged(dt, c2, s.m2, s.i2, w.bn2.gamma, w.bn2.beta, 0, cr, s.mr, s.ir, w.bnr.gamma, w.bnr.beta, 0, y, pad_y, B, Tout, O, 1, lens, 4 >> i, stream);
+            return ss_bn_apply(dt, c2, s.m2, s.i2, w.bn2.gamma, w.bn2.beta, 0, cr, s.mr, s.ir, w.bnr.gamma, w.bnr.beta, 0, y, pad_y, B, Tout, O, 1, stream); }));
         s.c1 = c1; s.cr = cr; s.h1 = h1; s.c2 = c2; s.y = y; s.pad_y = pad_y;
         xin = y; Tin = Tout; Cin = O;
     }
@@ -402,8 +414,12 @@ int Plan::forward(Exec& X, const float* x_raw, float* shifted, int B, int T0, in
     const int Tp = round_up(T, 8);
     const float scale = 1.0f / sqrtf((float)D.d_qkv);
     c->Tp = Tp; c->scale = scale;
-    const bool x3att = use_x3_attention(T);
-    c->need_T = x3att ? 0 : ss_relpos_attention_needs_transposed(dt, T, dp, Dr);
+    // a ragged batch always runs the per-tile attention kernels (the only family that takes lengths): the QKV GEMM always writes the transposed copy and the
+    // attention never runs on planes
+    const bool x3att = !ragged && use_x3_attention(T);
+    c->need_T = ragged ? 1 : (x3att ? 0 : ss_relpos_attention_needs_transposed(dt, T, dp, Dr));
+    double pairs = (double)B * band_pairs(T, Dr);            // (query, key) pairs of one head: from the real lengths when the caller has them on the host
+    if (ragged && lens_host && !X.dry) { pairs = 0; for (int b = 0; b < B; ++b) pairs += band_pairs(lens_host[b] < T ? lens_host[b] : T, Dr); }
     for (int l = 0; l < D.n_layers; ++l) {
         LayerP& w = layers[l]; LayerCtx& s = c->layer[l];
         s.x = x;
@@ -415,7 +431,7 @@ int Plan::forward(Exec& X, const float* x_raw, float* shifted, int B, int T0, in
             L_(gemm(X, dt, x, w.wqkv, qkv, M, 3 * HD, d, RM(d), RM(d), RM(3 * HD), &e));
         } else L_(gemm(X, dt, x, w.wqkv, qkv, M, 3 * HD, d, RM(d), RM(d), RM(3 * HD), nullptr, SS_OP_KC, SS_OP_KC, 1, 0, nullptr, x3att ? 2 : 0));      // x3 attention: qkv exists as planes only
         void* o = X.alloc((size_t)M * HD * es);
-        float* lse = (float*)X.alloc((size_t)B * H * T * 4);
+        float* lse = ragged ? nullptr : (float*)X.alloc((size_t)B * H * T * 4);      // (saved for the backward: an inference-only forward stores none)
         // training: the resident forward leaves its probabilities for the backward kernels (no recomputation of the logits there)
         const size_t pimg_bytes = training ? (size_t)(x3att ? ss_relpos_attention_x3_saved_bytes(B, H, T, dp, Dr) : ss_relpos_attention_saved_bytes(dt, B, H, T, dp, Dr)) : 0;
         void* pimg = pimg_bytes ? X.alloc(pimg_bytes) : nullptr;
@@ -427,6 +443,8 @@ int Plan::forward(Exec& X, const float* x_raw, float* shifted, int B, int T0, in
                 if (!q.hi) return 1;
                 L_(timed(X, "attn_fwd", 2.0 * B * H * band_pairs(T, Dr) * dp * 3.0, (double)M * 4 * HD * es, stream, [&] { return ss_relpos_attention_x3_forward(q.hi, q.lo, w.EF, o, (char*)o + (size_t)M * HD * 2, lse, pimg, B, H, T, dp, Dr, scale, p_drop, seed, 4 * l, stream); }));
             }
+        } else if (ragged) {
+            if (!X.dry) L_(timed(X, "attn_fwd_ragged", 2.0 * H * pairs * dp * 3.0, (double)M * 4 * HD * es, stream, [&] { return ss_relpos_attention_forward_ragged(dt == SS_F32 && f32_x3 ? SS_F32X3 : dt, qkv, qkvT, w.E, o, lens, B, H, T, Tp, dp, Dr, scale, stream); }));
         } else
         if (!X.dry) L_(timed(X, "attn_fwd", 2.0 * B * H * band_pairs(T, Dr) * dp * 3.0, (double)M * 4 * HD * es, stream, [&] { return ss_relpos_attention_forward_p(dt == SS_F32 && f32_x3 ? SS_F32X3 : dt, qkv, qkvT, w.E, w.EF, o, lse, pimg, B, H, T, Tp, dp, Dr, scale, p_drop, seed, 4 * l, stream); }));
         s.pimg = pimg;
@@ -727,22 +745,55 @@ extern "C" int64_t ss_plan_workspace_bytes(ss_plan* h, int B, int T0, int traini
     return (int64_t)((X.off + 255) & ~(size_t)255) + 256;
 }
 
-extern "C" int ss_plan_forward(ss_plan* h, const float* x_raw, float* shifted_scratch, void* workspace, int64_t workspace_bytes, int B, int T0, int training, int shift_r,
-                               float dropout_p, uint64_t seed, float* head, void* ctx_out, void* stream)
+// every slot a forward pass reads is bound (gradient buffers, staging and un-layout tables belong to the backward)
+static int forward_slots_bound(const ss_plan* h, const char* what)
 {
-    SS_CHECK(h && x_raw && workspace && head && ctx_out, "ss_plan_forward: null pointer");
     for (size_t i = 0; i < h->p->targets.size(); ++i) {
         const std::string& n = h->p->names[i];
         const bool optional = n.find(".grad") != std::string::npos || n.find(".stage") != std::string::npos || n.find("unpack") != std::string::npos || n.find("stage_arena") != std::string::npos ||
                               n.find("num_batches_tracked") != std::string::npos;
-        SS_CHECK(*h->p->targets[i] || optional, "ss_plan_forward: slot '%s' is not bound", n.c_str());
+        SS_CHECK(*h->p->targets[i] || optional, "%s: slot '%s' is not bound", what, n.c_str());
     }
+    return 0;
+}
+
+extern "C" int ss_plan_forward(ss_plan* h, const float* x_raw, float* shifted_scratch, void* workspace, int64_t workspace_bytes, int B, int T0, int training, int shift_r,
+                               float dropout_p, uint64_t seed, float* head, void* ctx_out, void* stream)
+{
+    SS_CHECK(h && x_raw && workspace && head && ctx_out, "ss_plan_forward: null pointer");
+    if (forward_slots_bound(h, "ss_plan_forward")) return 1;
     Exec X{false, (char*)workspace, 0, (size_t)workspace_bytes, stream, nullptr};
     Ctx* c = (Ctx*)ctx_out; memset(c, 0, sizeof(Ctx));
     c->ws = (char*)workspace; c->ws_bytes = (unsigned long long)workspace_bytes;
     const int64_t need = ss_plan_workspace_bytes(h, B, T0, training);
     SS_CHECK(need >= 0 && need <= workspace_bytes, "ss_plan_forward: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)need);
     return h->p->forward(X, x_raw, shifted_scratch, B, T0, training, shift_r, dropout_p, seed, head, c);
+}
+
+extern "C" int64_t ss_plan_workspace_bytes_ragged(ss_plan* h, int B, int T0)
+{
+    if (!h) return -1;
+    Exec X{true, nullptr, 0, 0, nullptr, nullptr};
+    Ctx c; memset(&c, 0, sizeof(c));
+    if (h->p->forward(X, nullptr, nullptr, B, T0, 0, 0, 0.f, 0, nullptr, &c, true)) return -1;
+    return (int64_t)((X.off + 255) & ~(size_t)255) + 256;
+}
+
+extern "C" int ss_plan_forward_ragged(ss_plan* h, const float* x_raw, const int32_t* lens_dev, const int32_t* lens_host, void* workspace, int64_t workspace_bytes,
+                                      int B, int T0, float* head, void* stream)
+{
+    SS_CHECK(h && x_raw && lens_dev && workspace && head, "ss_plan_forward_ragged: null pointer");
+    SS_CHECK(B > 0 && T0 > 0, "ss_plan_forward_ragged: empty batch");
+    if (forward_slots_bound(h, "ss_plan_forward_ragged")) return 1;
+    if (lens_host) for (int b = 0; b < B; ++b) SS_CHECK(lens_host[b] >= 1 && lens_host[b] <= T0 / 8, "ss_plan_forward_ragged: utterance %d has %d frames, slots hold %d", b, lens_host[b], T0 / 8);
+    const int64_t need = ss_plan_workspace_bytes_ragged(h, B, T0);
+    SS_CHECK(need >= 0 && need <= workspace_bytes, "ss_plan_forward_ragged: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)need);
+    Exec X{false, (char*)workspace, 0, (size_t)workspace_bytes, stream, nullptr};
+    Ctx c; memset(&c, 0, sizeof(c));           // saved-for-backward pointers: nothing reads them after an inference forward
+    c.ws = (char*)workspace; c.ws_bytes = (unsigned long long)workspace_bytes;
+    const int rc = h->p->forward(X, x_raw, nullptr, B, T0, 0, 0, 0.f, 0, head, &c, true, lens_dev, lens_host);
+    h->p->cur = nullptr;
+    return rc;
 }
 
 extern "C" int ss_plan_backward(ss_plan* h, void* ctx, const float* dhead, void* stream, void* side_stream)

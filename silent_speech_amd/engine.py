@@ -410,6 +410,46 @@ class Ctx(object):
         self.buf, self.ws, self.M = buf, ws, M
 
 
+def _set_forward_options(pb, model, pr):
+    L = pb.lib
+    L.ss_plan_set_option(pb.handle, 5, int(model.f32_matmul == 'bf16x3'))         # (before the sizing pass: the plane form of that mode allocates operand planes)
+    L.ss_plan_set_option(pb.handle, 7, int(os.environ.get('SS_AMD_X3_PLANES', '1') != '0'))
+    L.ss_plan_set_option(pb.handle, 9, int(os.environ.get('SS_AMD_X3_EMIT', '1') != '0'))           # plane GEMMs write their consumers' planes from the epilogue (A/B: 0 = split passes)
+    L.ss_plan_set_option(pb.handle, 10, int(os.environ.get('SS_AMD_SIGN_GATE', '1') != '0'))        # FFN ReLU / dropout gate as sign bits (A/B: 0 = the saved activation)
+    L.ss_plan_set_option(pb.handle, 8, int(bool(pr.layers) and all(e['EF.x3'] for e in pr.layers) and os.environ.get('SS_AMD_X3_ATTENTION', '1') != '0'))
+    L.ss_plan_set_option(pb.handle, 1, int(os.environ.get('SS_AMD_DW_GROUPED', '1') != '0'))
+
+
+def forward_ragged(model, x_raw, lens, lens_host=None):
+    """Eval-mode forward of a ragged batch of whole utterances in ONE native call (ss_plan_forward_ragged).  x_raw (B, 8 T_max, 8) f32: utterance b
+    fills the first 8 lens[b] samples of slot b, zeros behind them; lens (B,) int32 on the same device -> head [B T_max][n_head_cols] f32 whose rows
+    [b T_max, b T_max + lens[b]) are what forward() gives for utterance b alone; the other rows of a slot are unspecified.  lens_host (optional, the
+    same lengths on the host) only feeds the attention row of the plan's profile.  Nothing is saved: there is no backward."""
+    pr = prepared(model)
+    dev = x_raw.device
+    B, T0, _ = x_raw.shape
+    if T0 % 8 != 0:
+        raise ValueError('raw EMG length %d must be a multiple of 8 (three stride-2 convolutions)' % T0)
+    if lens.dtype != torch.int32 or lens.shape != (B,) or lens.device != dev or not lens.is_contiguous():
+        raise ValueError('lens must be a contiguous int32 tensor of one length per utterance on the device of x_raw')
+    pb = plan_binding(model)
+    pb.ensure_bound(model, pr, None, dev)
+    pb.set_reduce_hook(None)
+    L = pb.lib
+    _set_forward_options(pb, model, pr)
+    nbytes = int(L.ss_plan_workspace_bytes_ragged(pb.handle, B, T0))
+    if nbytes < 0:
+        raise RuntimeError('ss_plan_workspace_bytes_ragged failed: %s' % L.ss_last_error().decode())
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    head = torch.empty(B * (T0 // 8), pr.n_head_cols, dtype=torch.float32, device=dev)
+    host = None
+    if lens_host is not None:
+        host = (ctypes.c_int32 * B)(*[int(n) for n in lens_host])
+    rc = L.ss_plan_forward_ragged(pb.handle, _lib.ptr(x_raw), _lib.ptr(lens), host, _lib.ptr(ws), nbytes, B, T0, _lib.ptr(head), _lib.stream_of(x_raw))
+    _lib.check(rc, 'ss_plan_forward_ragged')
+    return head
+
+
 def forward(model, x_raw, training, shift_r, seed):
     """x_raw (B, 8T, 8) f32 on the GPU -> head [B*T][n_head_cols] f32, the saved context (None in eval mode) and the time-shifted input
     (None without a shift).  x_raw itself is NOT modified (plan option 6): the caller mirrors the reference's in-place shift."""
@@ -426,12 +466,7 @@ def forward(model, x_raw, training, shift_r, seed):
     pb.ensure_bound(model, pr, gu, dev)
     pb.set_reduce_hook(model._bn_reduce_fn if training else None)
     L = pb.lib
-    L.ss_plan_set_option(pb.handle, 5, int(model.f32_matmul == 'bf16x3'))         # (before the sizing pass: the plane form of that mode allocates operand planes)
-    L.ss_plan_set_option(pb.handle, 7, int(os.environ.get('SS_AMD_X3_PLANES', '1') != '0'))
-    L.ss_plan_set_option(pb.handle, 9, int(os.environ.get('SS_AMD_X3_EMIT', '1') != '0'))           # plane GEMMs write their consumers' planes from the epilogue (A/B: 0 = split passes)
-    L.ss_plan_set_option(pb.handle, 10, int(os.environ.get('SS_AMD_SIGN_GATE', '1') != '0'))        # FFN ReLU / dropout gate as sign bits (A/B: 0 = the saved activation)
-    L.ss_plan_set_option(pb.handle, 8, int(bool(pr.layers) and all(e['EF.x3'] for e in pr.layers) and os.environ.get('SS_AMD_X3_ATTENTION', '1') != '0'))
-    L.ss_plan_set_option(pb.handle, 1, int(os.environ.get('SS_AMD_DW_GROUPED', '1') != '0'))
+    _set_forward_options(pb, model, pr)
     nbytes = int(L.ss_plan_workspace_bytes(pb.handle, B, T0, int(training)))
     if nbytes < 0:
         raise RuntimeError('ss_plan_workspace_bytes failed: %s' % L.ss_last_error().decode())

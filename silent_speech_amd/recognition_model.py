@@ -129,10 +129,32 @@ def wer(references, predictions):
     return errs / max(words, 1)
 
 
-def test(model, testset, device, *, batch_size=1):
+def greedy_decode_utterances(logits):
+    """Best-path decode of the per-utterance logits Model.forward_utterances returns -- (T_b, V) views of ONE (B T_max, >= V) head buffer --: one
+    per-frame arg-max launch over all slots (ss_frame_lse) and ONE read-back for the group, then collapse-repeats / drop-blanks per utterance on
+    the host over its own T_b frames (the filler rows of a slot are never looked at).  blank = V - 1.  Returns a list of int lists."""
+    if not logits:
+        return []
+    head, V = logits[0]._base, logits[0].shape[1]
+    B, T = len(logits), max(int(y.shape[0]) for y in logits)                 # the slots are as long as the longest utterance
+    if head is None or head.dim() != 2 or head.dtype != torch.float32 or not head.is_contiguous() or head.shape[0] != B * T or \
+            any(y._base is not head or y.shape[1] != V or y.storage_offset() != b * T * head.shape[1] for b, y in enumerate(logits)):
+        raise ValueError('greedy_decode_utterances takes the list Model.forward_utterances returned')
+    ld = head.shape[1]
+    lse = torch.empty(B * T, dtype=torch.float32, device=head.device)
+    amax = torch.empty(B * T, dtype=torch.int32, device=head.device)
+    _lib.check(_L().ss_frame_lse(_p(head), ld, 0, V, B * T, _p(lse), _p(amax), _lib.stream_of(head)), 'ss_frame_lse')
+    path = amax.cpu().numpy().reshape(B, T)
+    return [_collapse(path[b, :y.shape[0]], V - 1) for b, y in enumerate(logits)]
+
+
+def test(model, testset, device, *, batch_size=1, whole_utterances=False):
     """:30-58.  Default (batch_size=1) = the reference: eval-mode forward of ONE WHOLE utterance at a time (:37-43), so the convolutions
     and the +-99-frame attention band span the utterance (the banded attention kernels take any T).  batch_size > 1 packs the utterances
     into 200-frame rows like training does -- faster, but context is cut at the row boundaries, so its WER is not the reference's number.
+    whole_utterances=True with batch_size > 1: groups of up to batch_size WHOLE utterances go through Model.forward_utterances (one ragged-batch
+    plan call per group, every utterance computed as it is alone) and one arg-max launch + one read-back per group: the function of the
+    default, at batched speed.
     Decoding is greedy best-path in both cases (the reference's KenLM beam search is third-party C++ needing lm.binary: out of scope)."""
     model.eval()
     tt = testset.text_transform
@@ -148,6 +170,13 @@ def test(model, testset, device, *, batch_size=1):
                 pred = model(X, X_raw, sess)                                   # (1, T, V) logits
                 predictions.append(tt.int_to_text(greedy_decode(pred, [pred.shape[1]], blank)[0]))
                 references.append(tt.int_to_text(torch.as_tensor(ex['text_int']).tolist()))
+        elif whole_utterances:
+            for first in range(0, len(testset), batch_size):
+                group = [testset[i] for i in range(first, min(first + batch_size, len(testset)))]
+                logits = model.forward_utterances([ex['raw_emg'].to(dtype=torch.float32) for ex in group])
+                for ints, ex in zip(greedy_decode_utterances(logits), group):
+                    predictions.append(tt.int_to_text(ints))
+                    references.append(tt.int_to_text(torch.as_tensor(ex['text_int']).tolist()))
         else:
             dataloader = torch.utils.data.DataLoader(testset, batch_size=batch_size, collate_fn=testset.collate_raw)
             for batch in dataloader:

@@ -1,6 +1,7 @@
 """PyTorch dispatcher registration of the hot path: `torch.ops.silent_speech.*` (torch.library custom ops over the C ABI).
 
     model_forward / model_backward   Model.forward (architecture.py:61-84) and what loss.backward() triggers: one native plan each
+    model_forward_ragged             the eval-mode forward of a batch of WHOLE utterances of different lengths in one native plan (inference only)
     dtw_loss                         transduction_model.py:98-157 (cost matrices in strip layout, DTW + backtrace, loss and d loss / d head)
     dtw_align                        align.py:16-34 on one device matrix
     ctc_loss                         recognition_model.py:96-101
@@ -106,6 +107,26 @@ def _model_bwd(ctx, dhead, g_shifted):
 
 
 model_forward.register_autograd(_model_bwd, setup_context=_model_setup)
+
+
+@torch.library.custom_op('silent_speech::model_forward_ragged', mutates_args=())
+def model_forward_ragged(x_raw: Tensor, lens: Tensor, handle: int) -> Tensor:
+    """Eval-mode forward (running BatchNorm statistics, no dropout, no shift) of B whole utterances in equal slots: x_raw (B, 8 T_max, 8) f32 with utterance
+    b in the first 8 lens[b] samples of slot b and zeros behind them, lens (B,) int32 on the same device -> head [B T_max][n_head_cols] f32.  Rows
+    [b T_max, b T_max + lens[b]) are exactly what model_forward gives for utterance b alone (its convolutions see zero padding at the utterance's end,
+    its attention sees its own keys only); the other rows are unspecified.  NOT differentiable: no autograd formula is registered and nothing is
+    saved -- training on ragged slots would need masked BatchNorm statistics and a backward pass."""
+    from . import engine
+    m = _model(handle)
+    host = getattr(m, '_ragged_lens_host', None)           # Model.forward_utterances leaves the lengths it uploaded: profile rows count real attention work
+    return engine.forward_ragged(m, x_raw, lens, host if host is not None and len(host) == x_raw.shape[0] else None)
+
+
+@model_forward_ragged.register_fake
+def _(x_raw, lens, handle):
+    m = _model(handle)
+    n_head_cols = (m.num_outs + (m.num_aux_outs or 0) + 7) // 8 * 8          # the fused heads, as engine.Prepared lays them out
+    return x_raw.new_empty((x_raw.shape[0] * (x_raw.shape[1] // 8), n_head_cols), dtype=torch.float32)
 
 
 # ------------------------------------------------------------------------------------------------ dtw_loss
@@ -316,5 +337,5 @@ def _(x, w, k, slope):
     return x.new_empty((x.shape[0],))
 
 
-OPS = ('model_forward', 'model_backward', 'dtw_loss', 'dtw_align', 'ctc_loss', 'stft_logmel', 'emg_features', 'fused_adamw',
+OPS = ('model_forward', 'model_forward_ragged', 'model_backward', 'dtw_loss', 'dtw_align', 'ctc_loss', 'stft_logmel', 'emg_features', 'fused_adamw',
        'vocoder_conv1d', 'vocoder_conv_transpose1d', 'vocoder_tail')

@@ -4,6 +4,7 @@
     test(model, testset, device)                                                                       (:33-55)
     train_model(trainset, devset, device, save_sound_outputs=True)                                     (:159-227)
     save_output(model, datapoint, filename, device, audio_normalizer, vocoder)                         (:57-73)
+    predict_utterances / save_outputs: the same for a LIST of utterances, the model forward as ragged batches (Model.forward_utterances)
 
 dtw_loss keeps everything on the GPU: cost matrices are produced directly in the DTW kernel's strip
 layout, DTW + backtrace run on device, and loss/gradient touch only the aligned pairs -- no D2H copy
@@ -246,6 +247,16 @@ class EnsembleModel(torch.nn.Module):
             ps.append(p)
         return torch.stack(ys, 0).mean(0), torch.stack(ps, 0).mean(0)
 
+    def forward_utterances(self, raws):
+        """Model.forward_utterances of every member, averaged per utterance as forward does."""
+        raws = list(raws)
+        if not raws:
+            return [], []
+        outs = [model.forward_utterances(raws) for model in self.models]
+        ys = [torch.stack([o[0][u] for o in outs], 0).mean(0) for u in range(len(raws))]
+        ps = [torch.stack([o[1][u] for o in outs], 0).mean(0) for u in range(len(raws))]
+        return ys, ps
+
 
 def predict_utterance(model, datapoint, device):
     """The model half of save_output (transduction_model.py:57-66): eval-mode forward of ONE whole utterance
@@ -260,6 +271,53 @@ def predict_utterance(model, datapoint, device):
         pred, _ = model(X, X_raw, sess)
     model.train(was_training)
     return pred.squeeze(0)
+
+
+MAX_SLOT_FRAMES = 22050        # B * T_max of a ragged group: the frames of one training step (110 rows of 200 + 50 more), whose workspace is known to fit
+MAX_PADDING = 0.25             # share of a group's slot frames that may be filler
+
+
+def plan_ragged_groups(lengths, max_slot_frames=MAX_SLOT_FRAMES, max_padding=MAX_PADDING):
+    """Cuts utterances of `lengths` frames into ragged batches: indices sorted by length (ties by index), then greedily grown groups that keep
+    B * T_max <= max_slot_frames and (B * T_max - sum T_b) / (B * T_max) <= max_padding.  A single utterance is always a valid group, whatever
+    its length.  Pure host logic, deterministic; returns a list of index lists that partitions range(len(lengths))."""
+    order = sorted(range(len(lengths)), key=lambda i: (int(lengths[i]), i))
+    groups, cur, total = [], [], 0
+    for i in order:
+        n = int(lengths[i])
+        if n < 1:
+            raise ValueError('utterance %d has no frames' % i)
+        # ascending order: the newcomer is the longest member, so it sets the slot length
+        slots = (len(cur) + 1) * n
+        if cur and (slots > max_slot_frames or (slots - total - n) > max_padding * slots):
+            groups.append(cur)
+            cur, total = [], 0
+        cur.append(i)
+        total += n
+    if cur:
+        groups.append(cur)
+    return groups
+
+
+def predict_utterances(model, datapoints, device, *, max_slot_frames=MAX_SLOT_FRAMES, max_padding=MAX_PADDING):
+    """predict_utterance for a list of datapoints: the eval-mode whole-utterance forward of every one, run as ragged batches
+    (plan_ragged_groups + Model.forward_utterances: one native plan call per group instead of one per utterance).  Returns the (T_b, n_mel)
+    predictions on the device, in input order; each equals predict_utterance on that datapoint.  The model is returned to the mode it was in."""
+    datapoints = list(datapoints)
+    was_training = model.training
+    model.eval()
+    out = [None] * len(datapoints)
+    try:
+        with torch.no_grad():
+            raws = [d['raw_emg'] if d['raw_emg'].dtype == torch.float32 else d['raw_emg'].float() for d in datapoints]
+            for group in plan_ragged_groups([r.shape[0] // 8 for r in raws], max_slot_frames, max_padding):
+                res = model.forward_utterances([raws[i] for i in group])
+                preds = res[0] if isinstance(res, tuple) else res
+                for i, y in zip(group, preds):
+                    out[i] = y
+    finally:
+        model.train(was_training)
+    return out
 
 
 def _inverse_on_device(audio_normalizer, y):
@@ -290,6 +348,19 @@ def save_output(model, datapoint, filename, device, audio_normalizer, vocoder):
     with torch.no_grad():
         audio = vocoder(_inverse_on_device(audio_normalizer, y))
     write_wav(filename, audio.cpu().numpy())
+
+
+def save_outputs(model, datapoints, filenames, device, audio_normalizer, vocoder):
+    """save_output for a list of utterances: ragged-batch model forward (predict_utterances), the inverse normaliser on the device, ONE batched
+    vocoder call (Vocoder.batch) and a wav per utterance."""
+    datapoints, filenames = list(datapoints), list(filenames)
+    if len(datapoints) != len(filenames):
+        raise ValueError('one filename per datapoint')
+    ys = predict_utterances(model, datapoints, device)
+    with torch.no_grad():
+        audios = vocoder.batch([_inverse_on_device(audio_normalizer, y) for y in ys]) if ys else []
+    for filename, audio in zip(filenames, audios):
+        write_wav(filename, audio.cpu().numpy())
 
 
 def get_aligned_prediction(model, datapoint, device, audio_normalizer):
