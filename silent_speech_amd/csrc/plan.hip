@@ -344,7 +344,8 @@ int Plan::forward(Exec& X, const float* x_raw, float* shifted, int B, int T0, in
     // Ragged batch (ss_plan_forward_ragged): utterance b fills the first lens[b] model frames of slot b.  The layout, the row maps, the GEMMs, LayerNorm and the
     // heads are those of a dense batch; two kernels take the lengths: every BatchNorm apply stores zeros behind an utterance's end (valid rows per slot:
     // 4, 2, 1 x lens[b] in the three blocks), so that the right tap of each k = 3 convolution reads the zero padding the utterance has when it runs alone, and the
-    // attention bounds its keys by lens[b].  Everything else works row by row: the filler rows of a slot hold finite values nobody reads into a valid row.
+    // attention bounds its keys by lens[b].  Everything else works row by row.  The filler rows of a slot are unspecified and may be non-finite (the attention leaves its output rows behind an
+    // utterance's end as the workspace held them); valid rows are safe because everything behind an utterance's end is discarded by select, never by arithmetic (no multiplying by 0).
     SS_CHECK(!ragged || (!training && (X.dry || lens)), "ragged batches are eval-mode only and need their lengths");
     const int dt = D.dtype, d = D.d_model; const size_t es = esz();
     const int Cin0 = 8;

@@ -251,6 +251,16 @@ def bn_apply(xa, sa, pad_xa, y, pad_y, B, T, C, relu, xb=None, sb=None, pad_xb=0
     return y
 
 
+def bn_apply_ragged(xa, sa, pad_xa, y, pad_y, B, T, C, relu, lens, len_mul, xb=None, sb=None, pad_xb=0):
+    """bn_apply on B equal slots of T rows: sequence b owns rows t < lens[b] * len_mul (int32 on the device, clamped to [0, T]); zeros behind them."""
+    n4 = [None] * 4
+    b4 = sb if sb is not None else n4
+    rc = _L().ss_bn_apply_ragged(_dt(xa), _p(xa), _p(sa[0]), _p(sa[1]), _p(sa[2]), _p(sa[3]), pad_xa,
+                                 _p(xb), _p(b4[0]), _p(b4[1]), _p(b4[2]), _p(b4[3]), pad_xb, _p(y), pad_y, B, T, C, int(relu), _p(lens), len_mul, _s(xa))
+    _lib.check(rc, 'ss_bn_apply_ragged')
+    return y
+
+
 def bn_backward(dy, pad_dy, y, pad_y, xa, pad_xa, sa, dxa, pad_dxa, dgamma_a, dbeta_a, scratch, B, T, C, relu,
                 xb=None, pad_xb=0, sb=None, dxb=None, pad_dxb=0, dgamma_b=None, dbeta_b=None, reduce_fn=None, beta_a=None, beta_b=None):
     """sa/sb = (mean, invstd, gamma).  reduce_fn as in bn_stats (all-reduces the [3][C] gradient sums).  beta_a [, beta_b]: recompute
@@ -364,6 +374,13 @@ def relpos_attention_forward(qkv, qkvT, E, out, lse, B, H, T, Tp, dp, D, scale, 
     rc = _L().ss_relpos_attention_forward_p(_attn_dt(qkv, f32_math), _p(qkv), _p(qkvT), _p(E), _p(tab), _p(out), _p(lse), _p(saved), B, H, T, Tp, dp, D, scale, p,
                                             int(seed) & 0xFFFFFFFFFFFFFFFF, rng_stream, _s(qkv))
     _lib.check(rc, 'ss_relpos_attention_forward')
+
+
+def relpos_attention_forward_ragged(qkv, qkvT, E, out, lens, B, H, T, Tp, dp, D, scale, f32_math='exact'):
+    """Inference forward on B equal slots of T rows (always the per-tile kernels): sequence b is rows t < lens[b] (int32 on the device, clamped to
+    [0, T]) of slot b; the rows of out behind them are left as they were."""
+    rc = _L().ss_relpos_attention_forward_ragged(_attn_dt(qkv, f32_math), _p(qkv), _p(qkvT), _p(E), _p(out), _p(lens), B, H, T, Tp, dp, D, scale, _s(qkv))
+    _lib.check(rc, 'ss_relpos_attention_forward_ragged')
 
 
 def relpos_attention_backward(qkv, qkvT, E, ET, out, lse, dO, dOT, dscratch, dqkv, B, H, T, Tp, dp, D, scale, p=0.0, seed=0, rng_stream=0, saved=None,

@@ -110,6 +110,54 @@ def test_arithmetic_modes_gpu(kw, tol, frac):
     _check_each(preds, auxs, _oracle('tiny', sd, FULL), FULL, tol, frac)
 
 
+WIDE = [230, 121, 16, 5]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('kw,tol,frac', [(dict(compute_dtype=torch.float32), 2e-4, 0), (dict(compute_dtype=torch.float32, f32_matmul='bf16x3'), 2e-4, 0),
+                                         (dict(compute_dtype=torch.bfloat16), 8e-2, 1e-3)], ids=['f32', 'bf16x3', 'bf16'])
+def test_product_width_gpu(kw, tol, frac):
+    """The product's width, one layer: d_head 96 runs attn_fwd_ragged_kernel<.., 3> inside the plan, and C = 768 puts every BatchNorm apply of the first
+    ResBlock (4 x 922 rows of 96 chunks > 768 x 256 threads) on the multi-trip RowWalk form, across slot boundaries."""
+    from silent_speech_amd import _lib
+    _lib.load()
+    sd = model_ref.init_state_dict(d_model=768, num_layers=1, seed=4)
+    m = Model(112, 80, 48, model_size=768, num_layers=1, dropout=0.0, **kw)
+    m.load_state_dict(sd, strict=True)
+    m.to('cuda').eval()
+    preds, auxs = m.forward_utterances([r.to('cuda') for r in _raws(WIDE)])
+    _check_each(preds, auxs, _oracle('d768', sd, WIDE), WIDE, tol, frac)
+
+
+# ---------------------------------------------------------------------------------------------- 2b. recycled workspace
+def test_valid_rows_do_not_depend_on_what_the_workspace_held(dev, monkeypatch):
+    """engine.forward_ragged takes its workspace from torch.empty, i.e. recycled memory.  Here it arrives filled with 0xFF bytes -- NaN as f32 and as bf16:
+    every row the plan does not store (attention output rows behind an utterance's end, and what the row-wise kernels make of them) is then
+    non-finite, and the valid rows still meet the bar only because K rows, V^T fragments and BatchNorm inputs behind the end are discarded by select,
+    never multiplied by 0."""
+    lengths = [17, 9, 16] if is_emu(dev) else FULL
+    m, sd = _model(dev)
+    m.eval()
+    raws = [r.to(dev) for r in _raws(lengths)]
+    filled = []
+    real_empty = torch.empty
+    with monkeypatch.context() as mp:
+        def poisoned_empty(*a, **k):
+            t = real_empty(*a, **k)
+            if k.get('dtype') is torch.uint8:
+                t.fill_(0xFF)
+                filled.append(t.numel())
+            return t
+        mp.setattr(torch, 'empty', poisoned_empty)
+        preds, auxs = m.forward_utterances(raws)
+    assert torch.empty is real_empty
+    assert filled and max(filled) > 0                      # the wrapper saw (at least) the workspace
+    head = preds[0]._base.float().cpu().view(len(lengths), max(lengths), -1)
+    filler = torch.cat([head[b, T:] for b, T in enumerate(lengths)])
+    assert filler.shape[0] > 0 and not torch.isfinite(filler).all(), 'the poison never reached a filler row: this run proves nothing'
+    _check_each(preds, auxs, _oracle('tiny', sd, lengths), lengths, 2e-4)
+
+
 # ---------------------------------------------------------------------------------------------- 3. long utterances through the grouper
 @pytest.mark.gpu
 @pytest.mark.parametrize('dt,tol', [(torch.float32, 3e-4), (torch.bfloat16, 8e-2)])
