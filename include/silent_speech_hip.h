@@ -30,9 +30,9 @@ extern "C" {
 const char* ss_last_error(void);
 /* Library/ABI version and the GPU architecture the kernels were compiled for ("gfx950"). */
 /* Bumped whenever a struct layout or an entry-point signature changes (3: ss_gemm_epilogue column-statistics fields, the plan /
- * attention-image / LayerNorm-workspace entry points, ss_dtw_cumulative; 4: ss_loss_index_tables; 5: gate recomputation arguments of ss_bn_backward_sums / ss_bn_backward_apply; 7: ss_split_planes / ss_gemm_planes, ss_dw_job.flags, up to 24 jobs per grouped launch; 8: ss_stft_logmel_fft, the rejected-frame counter behind the matrix of ss_phoneme_confusion; 9: planes_hi / planes_lo / planes_only of ss_gemm_epilogue, dropout groups of the GEMM epilogue are row-major; 10: ss_emg_features_batch; 11: the ss_voc_* vocoder entry points; 12: the ragged-batch inference entry points ss_bn_apply_ragged, ss_relpos_attention_forward_ragged, ss_plan_forward_ragged).  Bindings must compare it with SS_ABI_VERSION at load time: a stale
+ * attention-image / LayerNorm-workspace entry points, ss_dtw_cumulative; 4: ss_loss_index_tables; 5: gate recomputation arguments of ss_bn_backward_sums / ss_bn_backward_apply; 7: ss_split_planes / ss_gemm_planes, ss_dw_job.flags, up to 24 jobs per grouped launch; 8: ss_stft_logmel_fft, the rejected-frame counter behind the matrix of ss_phoneme_confusion; 9: planes_hi / planes_lo / planes_only of ss_gemm_epilogue, dropout groups of the GEMM epilogue are row-major; 10: ss_emg_features_batch; 11: the ss_voc_* vocoder entry points; 12: the ragged-batch inference entry points ss_bn_apply_ragged, ss_relpos_attention_forward_ragged, ss_plan_forward_ragged; 13: ss_ctc_beam_search / ss_ctc_beam_workspace_bytes).  Bindings must compare it with SS_ABI_VERSION at load time: a stale
  * library paired with newer headers would otherwise read garbage struct fields instead of failing. */
-#define SS_ABI_VERSION 12
+#define SS_ABI_VERSION 13
 int ss_abi_version(void);
 const char* ss_target_arch(void);
 
@@ -345,6 +345,32 @@ int ss_phoneme_confusion(const int32_t* argmax, const int64_t* phones, const int
  * d loss / d logits (all `rows` x ld entries; zero outside the utterances). */
 int ss_ctc_loss(const float* logits, int64_t ld, int V, int blank, const float* lse, const int64_t* desc_dev, int n_utt, int max_target_len,
                 int64_t rows, const int32_t* targets, float* alpha_ws, float* beta_ws, float* nll, float* dlogits, float* loss, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * CTC prefix beam search with shallow fusion of a label n-gram table, the whole batch in one launch (csrc/ctc_decode.hip).
+ * Inputs: f32 logits (rows, ld), classes in columns 0 .. V-1 (V <= 128, ld >= V, further columns are never read); lse = per-frame
+ * log-sum-exp (ss_frame_lse with col0 = 0); blank in [0, V); utt_dev (device, int64 x2 per utterance) = first frame, frames -- the packed
+ * layout (utterances back to back) and the slot layout of ss_plan_forward_ragged (first frame = b * T_max) alike; frames behind an
+ * utterance's end are never read.  total_frames >= the sum of the frames (it sizes the workspace; an utterance that would exceed it, or
+ * leave [0, rows), is cut short, never read out of bounds).  Beam width 1 <= W <= 128, 1 <= n_best <= W.  lm (optional, device): f32
+ * natural-log probabilities (C+1, C+1, C), C = V-1 labels numbered with the blank skipped, context index C = "before the start"; all
+ * entries finite.
+ * Search: logp_t(c) = logit_t(c) - lse_t.  A beam entry is a label prefix with (lb, lnb), the log mass of its paths that end / do not end
+ * in blank; start: the empty prefix with (0, -inf).  Per frame, for every entry p with tot = lb (+) lnb ((+) = log-add-exp):
+ *   stay    lb'(p) (+)= tot + logp(blank); if p is not empty, lnb'(p) (+)= lnb + logp(last(p));
+ *   extend  by every label c != blank to q = p + c: lnb'(q) (+)= (c == last(p) ? lb : tot) + logp(c).
+ * A prefix reached by several routes is ONE candidate whose contributions are summed (q already in the beam while p + c produces it too).
+ * score(q) = lb' (+) lnb' + sum_i (alpha * lm[q_{i-2}, q_{i-1}, q_i] + beta), the sum 0 without a table.  A candidate of score -inf does
+ * not exist.  The W candidates of largest score survive; ties go to the lower candidate index (beam slot of p) * V + c (c = blank: p itself).
+ * Outputs for the n_best best entries after the last frame, best first (ties: beam slot): labels (n_utt, n_best, max_len) int32 class
+ * numbers, -1 behind the end (max_len >= the longest utterance's frames holds every string; longer strings keep their first max_len
+ * labels), lengths (n_utt, n_best), scores and their CTC part alone (n_utt, n_best) f32 natural log.  Ranks that do not exist: length -1,
+ * scores -inf.  An utterance of 0 frames yields the empty string with score 0.
+ * workspace: ss_ctc_beam_workspace_bytes(n_utt, total_frames, W) bytes (the prefix trie; needs no initialisation); -1 = bad arguments. */
+int64_t ss_ctc_beam_workspace_bytes(int n_utt, int64_t total_frames, int beam_width);
+int ss_ctc_beam_search(const float* logits, int64_t ld, int V, int blank, int64_t rows, const float* lse, const int64_t* utt_dev, int n_utt,
+                       int64_t total_frames, int beam_width, int n_best, const float* lm, float alpha, float beta, void* workspace, int max_len,
+                       int32_t* labels, int32_t* lengths, float* scores, float* ctc_scores, void* stream);
 
 /* AdamW over a flat f32 arena (transduction_model.py:178,210).  step is 1-based. */
 int ss_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.environ.get('SS_AMD_LIBRARY') or os.path.join(_HERE, 'lib', 'libsilent_speech_hip.so')      # override: A/B runs of two builds on one box
 
 SS_F32, SS_BF16, SS_F64, SS_F32X3 = 0, 1, 2, 3
-ABI_VERSION = 12         # include/silent_speech_hip.h: SS_ABI_VERSION (struct layouts / signatures this binding was written against)
+ABI_VERSION = 13         # include/silent_speech_hip.h: SS_ABI_VERSION (struct layouts / signatures this binding was written against)
 OP_KC, OP_OC = 0, 1
 
 
@@ -99,6 +99,7 @@ SIGNATURES = {
     'ss_silent_loss': [_P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _F, _F, _P, _P, _P, _P],
     'ss_phoneme_confusion': [_P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _P],
     'ss_ctc_loss': [_P, _L, _I, _I, _P, _P, _I, _I, _L, _P, _P, _P, _P, _P, _P, _P],
+    'ss_ctc_beam_search': [_P, _L, _I, _I, _L, _P, _P, _I, _L, _I, _I, _P, _F, _F, _P, _I, _P, _P, _P, _P, _P],
     'ss_adamw_step': [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _F, _P],
     'ss_cast_f32': [_P, _P, _I, _L, _P],
     'ss_soft_clip': [_P, _P, _L, _I, _P, _P, _F, _F, _P],
@@ -148,6 +149,7 @@ _HOST_FUNCS = {'ss_dtw_workspace_bytes': ([_I, _I, _LP, _LP, _LP], ctypes.c_int6
                'ss_relpos_attention_x3_saved_bytes': ([_I, _I, _I, _I, _I], ctypes.c_int64),
                'ss_relpos_attention_x3_table_bytes': ([_I, _I, _I], ctypes.c_int64),
                'ss_relpos_attention_saved_bytes': ([_I, _I, _I, _I, _I, _I], ctypes.c_int64),
+               'ss_ctc_beam_workspace_bytes': ([_I, _L, _I], ctypes.c_int64),
                'ss_voc_blob_bytes': ([_I, _I, _I], ctypes.c_int64),
                'ss_voc_workspace_bytes': ([_L, _I, ctypes.POINTER(ctypes.c_int), _I], ctypes.c_int64),
                'ss_voc_supported': ([_I, _I, _I, _I, _I], ctypes.c_int),

@@ -180,6 +180,13 @@ __device__ __forceinline__ float fast_exp2(float x) {
     return __builtin_amdgcn_exp2f(x);
 #endif
 }
+__device__ __forceinline__ float fast_log2(float x) {               // v_log_f32
+#if defined(SS_EMU)
+    return log2f(x);
+#else
+    return __builtin_amdgcn_logf(x);
+#endif
+}
 __device__ __forceinline__ float fast_rcp(float x) {
 #if defined(SS_EMU)
     return 1.f / x;

@@ -32,13 +32,6 @@ constexpr int CTC_MAX_STATES = 1024, CTC_FC = 32;      // 8 compute waves of 128
 // 128 000-sample batch whose longest utterance has 860 frames.)
 namespace {
 constexpr float LOG2E_F = 1.4426950408889634f, LN2_F = 0.6931471805599453f;
-__device__ __forceinline__ float fast_log2(float x) {
-#if defined(SS_EMU)
-    return log2f(x);
-#else
-    return __builtin_amdgcn_logf(x);
-#endif
-}
 // log2(2^a + 2^b [+ 2^c]) on FINITE numbers: "minus infinity" is the sentinel CTC_NEG inside the scan (-1e30 absorbs every log-probability added to it,
 // 2^(x - CTC_NEG) never occurs with x > CTC_NEG as the larger argument is subtracted), so the per-frame chain carries no NaN guard and no branch --
 // the first version tested m == -inf per state and hipcc made each test a branch around the transcendentals: ~40 taken / not-taken branches per frame.

@@ -2,14 +2,19 @@
 
     ctc_loss(logits, example, blank)         the three loss lines :96-101 fused on the packed layout
     greedy_decode(logits, lengths, blank)    best-path CTC decode (argmax, collapse repeats, drop blanks)
-    test(model, testset, device)             :30-58 with the greedy decoder -> WER
+    beam_decode(logits, lengths, blank)      CTC prefix beam search on the device (csrc/ctc_decode.hip), optionally fused with a LabelNgramLM
+    beam_decode_utterances(logits)           the same for the list Model.forward_utterances returns
+    LabelNgramLM                             label trigram table counted from text, the language model of the beam search
+    test(model, testset, device)             :30-58 -> WER; decoder='greedy' (default) or 'beam'
     train_model(trainset, devset, device)    :61-117 (AdamW, warm-up, x2 gradient accumulation, MultiStepLR)
 
 The encoder is the same MI355X engine as the transduction trainer (Model without the aux head).  The CTC
 alpha/beta recursion and its gradient run in csrc/ctc.hip straight on the packed (rows*200, V) logits, so the
 decollate + pad_sequence copies and the (T_max, N, V) log-prob tensor of the reference never exist.
-The reference's KenLM beam search (ctcdecode + lm.binary, :33-35) is a third-party C++ dependency that is not
-vendored and needs a language-model file; it is out of scope (parity unpinned) -- test() reports greedy WER.
+The search of the reference's decoder (ctcdecode, :33-35,48-49) is here as a kernel of its own: a prefix beam search over whole batches
+in one launch, with shallow fusion of a label n-gram table that lives on the device (LabelNgramLM).  Its KenLM WORD language model
+(third-party C++ plus an lm.binary file) stays out of scope, so parity with the reference's WER stays unpinned; test() reports greedy
+WER by default and beam-search WER with decoder='beam'.
 """
 import logging
 import os
@@ -148,17 +153,122 @@ def greedy_decode_utterances(logits):
     return [_collapse(path[b, :y.shape[0]], V - 1) for b, y in enumerate(logits)]
 
 
-def test(model, testset, device, *, batch_size=1, whole_utterances=False):
+class LabelNgramLM(object):
+    """Label trigram table for the beam search: table[i2, i1, c] = ln P(label c | the two labels before it), f32 (C + 1, C + 1, C) over the
+    C labels of the text transform (the CTC classes with the blank skipped); context index C = "before the start of the text"."""
+
+    def __init__(self, table):
+        table = torch.as_tensor(table, dtype=torch.float32)
+        if table.dim() != 3 or table.shape[0] != table.shape[2] + 1 or table.shape[1] != table.shape[2] + 1:
+            raise ValueError('LabelNgramLM: a (C + 1, C + 1, C) table is expected')
+        self.table = table.contiguous()
+
+    @property
+    def n_labels(self):
+        return self.table.shape[2]
+
+    @classmethod
+    def from_texts(cls, texts, text_transform, add_k=0.1, order=3):
+        """Counts label n-grams over `texts` (each starting in the "before the start" context) and smooths every context with add_k:
+        P(c | context) = (count + add_k) / (context count + add_k C).  order 3 = trigram; 2 / 1 = bigram / unigram, stored in the same
+        table (constant along the leading axes they do not look at)."""
+        if order not in (1, 2, 3) or not add_k > 0:
+            raise ValueError('LabelNgramLM.from_texts: order 1, 2 or 3 and add_k > 0')
+        C = len(text_transform.chars)
+        counts = np.zeros((C + 1, C + 1, C), dtype=np.float64)
+        for text in texts:
+            i2 = i1 = C
+            for c in text_transform.text_to_int(text):
+                counts[i2 if order >= 3 else 0, i1 if order >= 2 else 0, c] += 1
+                i2, i1 = i1, c
+        if order < 3:
+            counts[:] = counts[:1]
+        if order < 2:
+            counts[:] = counts[:, :1]
+        prob = (counts + add_k) / (counts.sum(2, keepdims=True) + add_k * C)
+        return cls(torch.from_numpy(np.log(prob).astype(np.float32)))
+
+    def save(self, path):
+        with open(path, 'wb') as f:
+            np.savez(f, table=self.table.cpu().numpy())
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path) as z:
+            return cls(torch.from_numpy(z['table']))
+
+    def to(self, device):
+        return LabelNgramLM(self.table.to(device))
+
+
+def _beam_search(head, V, blank, first, frames, beam_width, n_best, lm, alpha, beta):
+    """One table upload, lse + search launches, one read-back.  head: (M, ld) f32 on the device; first / frames: per utterance, host ints."""
+    n = len(frames)
+    if n == 0:
+        return []
+    if lm is not None:
+        lm = (lm.table if isinstance(lm, LabelNgramLM) else torch.as_tensor(lm, dtype=torch.float32)).to(head.device).contiguous()
+    utt, = staging.upload([np.stack([np.asarray(first, dtype=np.int64), np.asarray(frames, dtype=np.int64)], 1)], head.device)
+    max_len = max(max(frames), 1)
+    labels, lengths, scores, _ = torch.ops.silent_speech.ctc_beam_search(head, utt, V, blank, int(sum(frames)), max_len, int(beam_width), int(n_best),
+                                                                         lm, float(alpha), float(beta))
+    back = torch.cat([labels.reshape(n, n_best * max_len), lengths, scores.view(torch.int32)], 1).cpu().numpy()       # ONE read-back
+    labels, lengths = back[:, :n_best * max_len].reshape(n, n_best, max_len), back[:, n_best * max_len:n_best * max_len + n_best]
+    scores = np.ascontiguousarray(back[:, n_best * max_len + n_best:]).view(np.float32)
+    if n_best == 1:
+        return [labels[b, 0, :max(lengths[b, 0], 0)].tolist() for b in range(n)]
+    return [[(labels[b, r, :lengths[b, r]].tolist(), float(scores[b, r])) for r in range(n_best) if lengths[b, r] >= 0] for b in range(n)]
+
+
+def beam_decode(pred, lengths, blank=None, *, beam_width=100, n_best=1, lm=None, alpha=0.0, beta=0.0):
+    """CTC prefix beam search of packed logits (rows, T, V) (NOT log-softmaxed), utterances back to back with `lengths` frames each, in one
+    launch on the device; lm: a LabelNgramLM (or its table) fused as alpha * ln P(label | two labels before) + beta per label.
+    Returns a list of int lists, or for n_best > 1 a list of [(ints, score), ...] lists, best first (fewer than n_best if fewer prefixes exist)."""
+    B, T, V = pred.shape
+    blank = V - 1 if blank is None else int(blank)
+    logits = pred.reshape(B * T, V).float().contiguous()
+    frames = [int(n) for n in lengths]
+    if sum(frames) > B * T or any(n < 0 for n in frames):
+        raise ValueError('beam_decode: the lengths do not fit the %d packed frames' % (B * T))
+    first = np.concatenate([[0], np.cumsum(frames)])[:-1] if frames else []
+    return _beam_search(logits, V, blank, first, frames, beam_width, n_best, lm, alpha, beta)
+
+
+def beam_decode_utterances(logits, *, beam_width=100, n_best=1, lm=None, alpha=0.0, beta=0.0):
+    """beam_decode for the per-utterance logits Model.forward_utterances returns -- (T_b, V) views of ONE (B T_max, >= V) head buffer --: the
+    search reads the slots in place (first frame b T_max, T_b frames; filler rows and columns are never looked at).  blank = V - 1."""
+    if not logits:
+        return []
+    head, V = logits[0]._base, logits[0].shape[1]
+    B, T = len(logits), max(int(y.shape[0]) for y in logits)
+    if head is None or head.dim() != 2 or head.dtype != torch.float32 or not head.is_contiguous() or head.shape[0] != B * T or \
+            any(y._base is not head or y.shape[1] != V or y.storage_offset() != b * T * head.shape[1] for b, y in enumerate(logits)):
+        raise ValueError('beam_decode_utterances takes the list Model.forward_utterances returned')
+    return _beam_search(head, V, V - 1, [b * T for b in range(B)], [int(y.shape[0]) for y in logits], beam_width, n_best, lm, alpha, beta)
+
+
+def test(model, testset, device, *, batch_size=1, whole_utterances=False, decoder='greedy', beam_width=100, lm=None, alpha=0.0, beta=0.0):
     """:30-58.  Default (batch_size=1) = the reference: eval-mode forward of ONE WHOLE utterance at a time (:37-43), so the convolutions
     and the +-99-frame attention band span the utterance (the banded attention kernels take any T).  batch_size > 1 packs the utterances
     into 200-frame rows like training does -- faster, but context is cut at the row boundaries, so its WER is not the reference's number.
     whole_utterances=True with batch_size > 1: groups of up to batch_size WHOLE utterances go through Model.forward_utterances (one ragged-batch
     plan call per group, every utterance computed as it is alone) and one arg-max launch + one read-back per group: the function of the
     default, at batched speed.
-    Decoding is greedy best-path in both cases (the reference's KenLM beam search is third-party C++ needing lm.binary: out of scope)."""
+    decoder='greedy' (default): best-path decoding.  decoder='beam': the prefix beam search of beam_decode / beam_decode_utterances with
+    beam_width, and lm / alpha / beta if a LabelNgramLM is given, in all three branches (the reference's KenLM word model is out of scope)."""
+    if decoder not in ('greedy', 'beam'):
+        raise ValueError("test: decoder is 'greedy' or 'beam'")
     model.eval()
     tt = testset.text_transform
     blank = len(tt.chars)
+    if decoder == 'beam':
+        lm = lm.to(device) if isinstance(lm, LabelNgramLM) else lm                  # the table crosses to the device once, not per utterance
+        search = dict(beam_width=beam_width, lm=lm, alpha=alpha, beta=beta)
+        decode = lambda pred, lengths: beam_decode(pred, lengths, blank, **search)
+        decode_utterances = lambda logits: beam_decode_utterances(logits, **search)
+    else:
+        decode = lambda pred, lengths: greedy_decode(pred, lengths, blank)
+        decode_utterances = greedy_decode_utterances
     references, predictions = [], []
     with torch.no_grad():
         if batch_size == 1:
@@ -168,13 +278,13 @@ def test(model, testset, device, *, batch_size=1, whole_utterances=False):
                 X_raw = ex['raw_emg'].to(device=device, dtype=torch.float32).unsqueeze(0)
                 sess = ex['session_ids'].to(device=device).unsqueeze(0)
                 pred = model(X, X_raw, sess)                                   # (1, T, V) logits
-                predictions.append(tt.int_to_text(greedy_decode(pred, [pred.shape[1]], blank)[0]))
+                predictions.append(tt.int_to_text(decode(pred, [pred.shape[1]])[0]))
                 references.append(tt.int_to_text(torch.as_tensor(ex['text_int']).tolist()))
         elif whole_utterances:
             for first in range(0, len(testset), batch_size):
                 group = [testset[i] for i in range(first, min(first + batch_size, len(testset)))]
                 logits = model.forward_utterances([ex['raw_emg'].to(dtype=torch.float32) for ex in group])
-                for ints, ex in zip(greedy_decode_utterances(logits), group):
+                for ints, ex in zip(decode_utterances(logits), group):
                     predictions.append(tt.int_to_text(ints))
                     references.append(tt.int_to_text(torch.as_tensor(ex['text_int']).tolist()))
         else:
@@ -182,7 +292,7 @@ def test(model, testset, device, *, batch_size=1, whole_utterances=False):
             for batch in dataloader:
                 X, X_raw, sess = prepare_batch(batch, device, loss_plan=False)
                 pred = model(X, X_raw, sess)
-                for ints, tgt in zip(greedy_decode(pred, batch['lengths'], blank), batch['text_int']):
+                for ints, tgt in zip(decode(pred, batch['lengths']), batch['text_int']):
                     predictions.append(tt.int_to_text(ints))
                     references.append(tt.int_to_text(tgt.tolist()))
     model.train()

@@ -5,6 +5,7 @@
     dtw_loss                         transduction_model.py:98-157 (cost matrices in strip layout, DTW + backtrace, loss and d loss / d head)
     dtw_align                        align.py:16-34 on one device matrix
     ctc_loss                         recognition_model.py:96-101
+    ctc_beam_search                  the search of recognition_model.py:33-35,48-49: CTC prefix beam search + label n-gram table, one launch per batch (inference only)
     stft_logmel                      data_utils.py:39-62
     emg_features                     data_utils.py:85-136 (get_emg_features; no autograd: the reference's features are numpy)
     fused_adamw                      torch.optim.AdamW over the flat parameter arena (transduction_model.py:178,210)
@@ -237,6 +238,55 @@ def _ctc_bwd(ctx, g_loss, g_dl, g_nll, g_amax):
 ctc_loss.register_autograd(_ctc_bwd, setup_context=_ctc_setup)
 
 
+# ------------------------------------------------------------------------------------------------ ctc_beam_search (inference only: no autograd)
+@torch.library.custom_op('silent_speech::ctc_beam_search', mutates_args=())
+def ctc_beam_search(logits: Tensor, utt: Tensor, V: int, blank: int, total_frames: int, max_len: int, beam_width: int, n_best: int,
+                    lm: Optional[Tensor], alpha: float, beta: float) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """CTC prefix beam search (ss_ctc_beam_search in include/silent_speech_hip.h states the algorithm).  logits [M][ld >= V] f32 raw model
+    outputs; utt [n][2] int64 on the device = (first frame, frames) per utterance, packed or slot layout; total_frames >= the sum of the
+    frames, max_len >= the longest utterance; lm: optional (V, V, V - 1) f32 table of natural-log label probabilities, weights alpha, beta.
+    Returns (labels [n][n_best][max_len] int32 with -1 behind the end, lengths [n][n_best] int32 (-1: no such rank), scores, CTC scores [n][n_best])."""
+    dev = logits.device
+    if logits.dim() != 2 or logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise RuntimeError('ctc_beam_search: logits must be a contiguous (frames, ld) float32 matrix')
+    if utt.dim() != 2 or utt.shape[1] != 2 or utt.dtype != torch.int64 or not utt.is_contiguous() or utt.device != dev:
+        raise RuntimeError('ctc_beam_search: utt must be a contiguous (n, 2) int64 table on the device of the logits')
+    if lm is not None and (lm.shape != (V, V, V - 1) or lm.dtype != torch.float32 or not lm.is_contiguous() or lm.device != dev):
+        raise RuntimeError('ctc_beam_search: the label table must be a contiguous (%d, %d, %d) float32 tensor on the device of the logits' % (V, V, V - 1))
+    # everything the launches below rely on is checked HERE: ss_frame_lse reads V columns at stride ld whatever it is told
+    if not (1 <= V <= min(logits.shape[1], 128)) or not (0 <= blank < V):
+        raise RuntimeError('ctc_beam_search: %d classes (1 .. min(row stride %d, 128)), blank %d' % (V, logits.shape[1], blank))
+    if not (1 <= beam_width <= 128) or not (1 <= n_best <= beam_width):
+        raise RuntimeError('ctc_beam_search: beam width %d (1 .. 128), n_best %d (1 .. beam width)' % (beam_width, n_best))
+    if max_len < 1 or total_frames < 0:
+        raise RuntimeError('ctc_beam_search: max_len %d, total_frames %d' % (max_len, total_frames))
+    M, ld = logits.shape
+    n = utt.shape[0]
+    st = _lib.stream_of(logits)
+    ws_bytes = _L().ss_ctc_beam_workspace_bytes(n, total_frames, beam_width)
+    if ws_bytes < 0:
+        raise RuntimeError('ctc_beam_search: beam width %d (1 .. 128)' % beam_width)
+    lse = torch.empty(max(M, 1), dtype=torch.float32, device=dev)
+    amax = torch.empty(max(M, 1), dtype=torch.int32, device=dev)
+    if M:
+        _lib.check(_L().ss_frame_lse(_p(logits), ld, 0, V, M, _p(lse), _p(amax), st), 'ss_frame_lse')
+    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
+    labels = torch.empty((n, n_best, max_len), dtype=torch.int32, device=dev)
+    lengths = torch.empty((n, n_best), dtype=torch.int32, device=dev)
+    scores = torch.empty((n, n_best), dtype=torch.float32, device=dev)
+    ctc_scores = torch.empty((n, n_best), dtype=torch.float32, device=dev)
+    _lib.check(_L().ss_ctc_beam_search(_p(logits), ld, V, blank, M, _p(lse), _p(utt) if n else None, n, total_frames, beam_width, n_best,
+                                       _p(lm), alpha, beta, _p(ws), max_len, _p(labels), _p(lengths), _p(scores), _p(ctc_scores), st), 'ss_ctc_beam_search')
+    return labels, lengths, scores, ctc_scores
+
+
+@ctc_beam_search.register_fake
+def _(logits, utt, V, blank, total_frames, max_len, beam_width, n_best, lm, alpha, beta):
+    n = utt.shape[0]
+    return (logits.new_empty((n, n_best, max_len), dtype=torch.int32), logits.new_empty((n, n_best), dtype=torch.int32),
+            logits.new_empty((n, n_best)), logits.new_empty((n, n_best)))
+
+
 # ------------------------------------------------------------------------------------------------ stft_logmel
 @torch.library.custom_op('silent_speech::stft_logmel', mutates_args=())
 def stft_logmel(y: Tensor, n_fft: int, num_mels: int, sampling_rate: int, hop_size: int, win_size: int, fmin: int, fmax: int, center: bool) -> Tensor:
@@ -337,5 +387,5 @@ def _(x, w, k, slope):
     return x.new_empty((x.shape[0],))
 
 
-OPS = ('model_forward', 'model_forward_ragged', 'model_backward', 'dtw_loss', 'dtw_align', 'ctc_loss', 'stft_logmel', 'emg_features', 'fused_adamw',
+OPS = ('model_forward', 'model_forward_ragged', 'model_backward', 'dtw_loss', 'dtw_align', 'ctc_loss', 'ctc_beam_search', 'stft_logmel', 'emg_features', 'fused_adamw',
        'vocoder_conv1d', 'vocoder_conv_transpose1d', 'vocoder_tail')
