@@ -68,9 +68,55 @@ def ctc_utterance(logp, target, blank):
     return nll, grad
 
 
-def ctc_loss_packed(logits, lengths, targets, blank):
+def ctc_utterance_vec(logp, target, blank):
+    """ctc_utterance with the states of a frame as one array operation: the same recursion, the same float64, the same return values
+    (pinned to the loop version by tests/test_oracle_golden.py); ~100 x faster at 1000 states."""
+    logp = np.asarray(logp, dtype=np.float64)
+    T, V = logp.shape
+    S = len(target)
+    ext = np.full(2 * S + 1, blank, dtype=np.int64)
+    ext[1::2] = target
+    SP = len(ext)
+    NEG = -np.inf
+    skip = np.zeros(SP, dtype=bool)                                      # state s also takes s - 2 (and, mirrored, s - 2 also feeds on s in beta)
+    skip[2:] = (ext[2:] != blank) & (ext[2:] != ext[:-2])
+    lpe = logp[:, ext]
+    alpha = np.full((T, SP), NEG)
+    beta = np.full((T, SP), NEG)
+    alpha[0, :2] = lpe[0, :2]
+    for t in range(1, T):
+        p = alpha[t - 1]
+        a = p.copy()
+        a[1:] = np.logaddexp(a[1:], p[:-1])
+        a[2:] = np.logaddexp(a[2:], np.where(skip[2:], p[:-2], NEG))
+        alpha[t] = a + lpe[t]
+    beta[T - 1, -2:] = lpe[T - 1, -2:]
+    for t in range(T - 2, -1, -1):
+        p = beta[t + 1]
+        b = p.copy()
+        b[:-1] = np.logaddexp(b[:-1], p[1:])
+        b[:-2] = np.logaddexp(b[:-2], np.where(skip[2:], p[2:], NEG))
+        beta[t] = b + lpe[t]
+    ll = np.logaddexp(alpha[T - 1, SP - 1], alpha[T - 1, SP - 2]) if SP > 1 else alpha[T - 1, SP - 1]
+    nll = -ll
+    ab = alpha + beta
+    lcab = np.full((T, V), NEG)                                          # scatter-logsumexp of alpha + beta into the class of each state
+    for c in np.unique(ext):
+        sel = ab[:, ext == c]
+        m = sel.max(1)
+        ms = np.where(np.isfinite(m), m, 0.0)
+        with np.errstate(divide='ignore'):
+            lcab[:, c] = np.where(np.isfinite(m), ms + np.log(np.exp(sel - ms[:, None]).sum(1)), m)
+    with np.errstate(invalid='ignore', over='ignore'):
+        grad = np.exp(logp) - np.exp(lcab + nll - logp)
+    return nll, grad
+
+
+def ctc_loss_packed(logits, lengths, targets, blank, vec=False):
     """logits (rows, row_len, V) packed frames (utterances back to back, data_utils.py:159-179) ->
-    (loss, dlogits of the same shape, nll per utterance); semantics of recognition_model.py:96-101."""
+    (loss, dlogits of the same shape, nll per utterance); semantics of recognition_model.py:96-101.
+    vec=True runs the recursion through ctc_utterance_vec."""
+    utterance = ctc_utterance_vec if vec else ctc_utterance
     logits = np.asarray(logits, dtype=np.float64)
     shp = logits.shape
     V = shp[-1]
@@ -83,7 +129,7 @@ def ctc_loss_packed(logits, lengths, targets, blank):
     n = len(lengths)
     for T, tgt in zip(lengths, targets):
         tgt = np.asarray(tgt, dtype=np.int64)
-        nll, g = ctc_utterance(logp[off:off + T], tgt, blank)
+        nll, g = utterance(logp[off:off + T], tgt, blank)
         d[off:off + T] = g / (max(len(tgt), 1) * n)
         nlls.append(nll)
         off += T

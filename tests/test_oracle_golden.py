@@ -199,3 +199,58 @@ def test_ctc_oracle_matches_reference(tag):
     nan = np.isnan(z['dlogits'])
     assert np.array_equal(np.isnan(d), nan)
     np.testing.assert_allclose(d[~nan], z['dlogits'][~nan], rtol=1e-4, atol=2e-7)
+
+
+def _ctc_pin_case(tag):
+    if tag.startswith('ctc_'):
+        z = np.load(os.path.join(GOLD, tag + '.npz'))
+        lengths = [int(n) for n in z['lengths']]
+        return z['logits'], lengths, [z['text/%d' % i] for i in range(len(lengths))], int(z['blank'])
+    rng = np.random.default_rng(11)
+    logits = 2.0 * rng.standard_normal((1, 14, 5))
+    target = [np.array([2, 2, 2, 1, 1])]                                  # three repeated neighbours: 8 frames at least
+    if tag == 'neg_inf_class':
+        logits[..., 3] = -np.inf                                          # a class of probability 0 that no target uses
+    return logits, [6 if tag == 'too_short' else 14], target, 0
+
+
+@pytest.mark.parametrize('tag', ['ctc_mixed', 'ctc_repeats', 'ctc_long', 'ctc_infeasible', 'repeated', 'too_short', 'neg_inf_class'])
+def test_ctc_vectorised_oracle_matches_loop(tag):
+    """ctc_utterance_vec (the states of a frame as one array operation) against the state-by-state loop it restates: the same inf / NaN pattern,
+    finite values to 1e-12 relative (both are float64; the loop sums a state's three predecessors at once, the array version two at a time),
+    and no numpy warning from the -inf arithmetic."""
+    import warnings
+    from oracle.ctc_ref import ctc_loss_packed
+    logits, lengths, targets, blank = _ctc_pin_case(tag)
+    want = ctc_loss_packed(logits, lengths, targets, blank)
+    with warnings.catch_warnings():
+        warnings.simplefilter('error')
+        got = ctc_loss_packed(logits, lengths, targets, blank, vec=True)
+    if tag in ('ctc_infeasible', 'too_short'):
+        assert np.isinf(want[2]).any()
+    if tag == 'neg_inf_class':
+        assert np.isnan(want[1][..., 3]).all() and np.isfinite(np.delete(want[1], 3, -1)).all()
+    for g, w in zip(got, want):
+        g, w = np.asarray(g, dtype=np.float64), np.asarray(w, dtype=np.float64)
+        assert np.array_equal(np.isnan(g), np.isnan(w)) and np.array_equal(np.isposinf(g), np.isposinf(w)) and np.array_equal(np.isneginf(g), np.isneginf(w))
+    (g_loss, g_d, g_nll), (w_loss, w_d, w_nll) = got, want
+    fin = np.isfinite(w_nll)
+    np.testing.assert_allclose(g_nll[fin], w_nll[fin], rtol=1e-12)
+    if fin.all():
+        np.testing.assert_allclose(g_loss, w_loss, rtol=1e-12)
+    # A gradient element is softmax - occupancy, both scaled by 1 / (max(S, 1) n): 1e-12 of the difference is not what either version can hold where
+    # the two cancel, so the bar is relative to the terms, |want| + occupancy.  The occupancy is exp(lcab + nll - logp), sums of magnitude |nll| whose
+    # rounding error is absolute: a few ulp(|nll|) of RELATIVE error in the exponential, which passes 1e-12 above |nll| ~ 300 (the 333-frame golden: 1.1e3).
+    V = np.shape(logits)[-1]
+    flat = np.asarray(logits, dtype=np.float64).reshape(-1, V)
+    sm = np.exp(flat - flat.max(1, keepdims=True))
+    sm /= sm.sum(1, keepdims=True)
+    off = 0
+    for T, t in zip(lengths, targets):
+        sm[off:off + T] /= max(len(t), 1) * len(lengths)
+        off += T
+    sm[off:] = 0.0
+    sm = sm.reshape(w_d.shape)
+    rtol = max(1e-12, 16 * np.finfo(np.float64).eps * float(np.max(np.abs(w_nll[fin]), initial=0.0)))
+    ok = np.isfinite(w_d)
+    assert (np.abs(g_d - w_d)[ok] <= rtol * (np.abs(w_d) + np.abs(sm - w_d))[ok]).all()
