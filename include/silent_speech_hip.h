@@ -30,9 +30,9 @@ extern "C" {
 const char* ss_last_error(void);
 /* Library/ABI version and the GPU architecture the kernels were compiled for ("gfx950"). */
 /* Bumped whenever a struct layout or an entry-point signature changes (3: ss_gemm_epilogue column-statistics fields, the plan /
- * attention-image / LayerNorm-workspace entry points, ss_dtw_cumulative; 4: ss_loss_index_tables; 5: gate recomputation arguments of ss_bn_backward_sums / ss_bn_backward_apply; 7: ss_split_planes / ss_gemm_planes, ss_dw_job.flags, up to 24 jobs per grouped launch; 8: ss_stft_logmel_fft, the rejected-frame counter behind the matrix of ss_phoneme_confusion; 9: planes_hi / planes_lo / planes_only of ss_gemm_epilogue, dropout groups of the GEMM epilogue are row-major; 10: ss_emg_features_batch; 11: the ss_voc_* vocoder entry points; 12: the ragged-batch inference entry points ss_bn_apply_ragged, ss_relpos_attention_forward_ragged, ss_plan_forward_ragged; 13: ss_ctc_beam_search / ss_ctc_beam_workspace_bytes).  Bindings must compare it with SS_ABI_VERSION at load time: a stale
+ * attention-image / LayerNorm-workspace entry points, ss_dtw_cumulative; 4: ss_loss_index_tables; 5: gate recomputation arguments of ss_bn_backward_sums / ss_bn_backward_apply; 7: ss_split_planes / ss_gemm_planes, ss_dw_job.flags, up to 24 jobs per grouped launch; 8: ss_stft_logmel_fft, the rejected-frame counter behind the matrix of ss_phoneme_confusion; 9: planes_hi / planes_lo / planes_only of ss_gemm_epilogue, dropout groups of the GEMM epilogue are row-major; 10: ss_emg_features_batch; 11: the ss_voc_* vocoder entry points; 12: the ragged-batch inference entry points ss_bn_apply_ragged, ss_relpos_attention_forward_ragged, ss_plan_forward_ragged; 13: ss_ctc_beam_search / ss_ctc_beam_workspace_bytes; 14: ss_word_lm, ss_ctc_word_beam_search / ss_ctc_word_beam_workspace_bytes, ss_word_ngram_score).  Bindings must compare it with SS_ABI_VERSION at load time: a stale
  * library paired with newer headers would otherwise read garbage struct fields instead of failing. */
-#define SS_ABI_VERSION 13
+#define SS_ABI_VERSION 14
 int ss_abi_version(void);
 const char* ss_target_arch(void);
 
@@ -371,6 +371,60 @@ int64_t ss_ctc_beam_workspace_bytes(int n_utt, int64_t total_frames, int beam_wi
 int ss_ctc_beam_search(const float* logits, int64_t ld, int V, int blank, int64_t rows, const float* lse, const int64_t* utt_dev, int n_utt,
                        int64_t total_frames, int beam_width, int n_best, const float* lm, float alpha, float beta, void* workspace, int max_len,
                        int32_t* labels, int32_t* lengths, float* scores, float* ctc_scores, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Word language model of the lexicon-constrained search below: a backoff n-gram over WORDS of order 1 .. 3 and the trie of their spellings,
+ * all arrays on the device, natural-log f32.  Word ids are 0 .. n_vocab - 1 for the words of the lexicon; `start` (the sentence-start
+ * context <s>) has an id of its own in [0, n_uni); every id is below 2^21.
+ *   lex_child (n_nodes, C) int32, C = V - 1 labels numbered with the blank skipped: child node or -1; node 0 is the root; the space's column is
+ *             all -1.  lex_word (n_nodes) int32: the id of the word spelled by the path to the node, or -1 (the root: -1).
+ *   uni_logp / uni_bo (n_uni): ln P(w) and the backoff weight of the context (w).
+ *   bi_* / tri_*: open-addressing hash tables, 64-bit keys (w1 << 21 | w; w2 << 42 | w1 << 21 | w), an all-ones key = empty slot, slot count a
+ *             power of two (or 0: no table, which makes an order-2 / order-1 model), home slot = splitmix64 finaliser of the key & (slots - 1),
+ *             linear probing that wraps around; *_probe = the longest probe sequence the builder needed, the lookup's loop bound.  Beside the
+ *             keys: bi_logp, bi_bo, tri_logp.
+ * ln P(w | w2, w1), w2 = -1 meaning "none": tri(w2, w1, w) if present; else (bo of bi(w2, w1), 0 if absent) + P2, P2 = bi(w1, w) if
+ * present, else uni_bo(w1) + uni_logp(w); with w2 = -1 it is P2, and with w1 = -1 too it is uni_logp(w).
+ * Every index formed from these tables is checked against the sizes given here: a malformed table gives wrong words, never a read outside
+ * the arrays. */
+typedef struct ss_word_lm {
+    const int32_t* lex_child;
+    const int32_t* lex_word;
+    const float* uni_logp;
+    const float* uni_bo;
+    const uint64_t* bi_keys;
+    const float* bi_logp;
+    const float* bi_bo;
+    const uint64_t* tri_keys;
+    const float* tri_logp;
+    int32_t n_nodes, n_vocab, n_uni, start;
+    int32_t bi_slots, bi_probe, tri_slots, tri_probe;
+} ss_word_lm;
+
+/* CTC prefix beam search confined to a lexicon, with a word n-gram scored at every word end (csrc/ctc_word_decode.hip; what the reference's
+ * ctcdecode does with a KenLM model, recognition_model.py:33-35 -- here from ARPA text or counted tables; parity with ctcdecode's own numbers
+ * is unpinned).  Inputs, layouts, lb / lnb, stay / extend, merging of a prefix reached by several routes, "a candidate of score -inf does
+ * not exist", ties to the lower candidate index, natural-log f32 and the outputs are those of ss_ctc_beam_search above.  Differences:
+ *   state    an entry additionally has a lexicon node and a word context (w2, w1); start: the root and (none, start).  Both are functions of
+ *            the label string, so merging is unchanged.  2 <= V, space in [0, V), space != blank.
+ *   letter   extending p by c (neither blank nor space) exists only if child = lex_child[node(p)][label(c)] is in [0, n_nodes); it becomes
+ *            the node; the LM score is unchanged.
+ *   space    extending p by the space exists only if w = lex_word[node(p)] is in [0, n_vocab) (no leading space, no double space):
+ *            LM score += alpha * ln P(w | w2, w1) + beta, the node returns to the root, the context becomes (w1, w).
+ *   end      after the last frame an entry is COMPLETE if it sits at the root or on a node with a word; in the second case the last word's
+ *            alpha * ln P + beta is added to its score (there is no </s> term).  Complete entries rank before incomplete ones, within each
+ *            group by score, ties to the lower beam slot.
+ * There is no out-of-vocabulary escape: every emitted word is a word of the lexicon.
+ * Additional output: complete (n_utt, n_best) int32 = 1 / 0, -1 for a rank that does not exist.
+ * workspace: ss_ctc_word_beam_workspace_bytes(n_utt, total_frames, W) bytes; -1 = bad arguments. */
+int64_t ss_ctc_word_beam_workspace_bytes(int n_utt, int64_t total_frames, int beam_width);
+int ss_ctc_word_beam_search(const float* logits, int64_t ld, int V, int blank, int space, int64_t rows, const float* lse, const int64_t* utt_dev,
+                            int n_utt, int64_t total_frames, int beam_width, int n_best, const ss_word_lm* lm, float alpha, float beta,
+                            void* workspace, int max_len, int32_t* labels, int32_t* lengths, float* scores, float* ctc_scores,
+                            int32_t* complete, void* stream);
+/* out[i] = ln P(w | w2, w1) of triples[i] = (w2, w1, w) (device, int32 x3) by the device function the search uses; an id outside the tables
+ * (w not in [0, n_uni), w1 / w2 not in [-1, n_uni)) gives NaN. */
+int ss_word_ngram_score(const ss_word_lm* lm, const int32_t* triples, int64_t n, float* out, void* stream);
 
 /* AdamW over a flat f32 arena (transduction_model.py:178,210).  step is 1-based. */
 int ss_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.environ.get('SS_AMD_LIBRARY') or os.path.join(_HERE, 'lib', 'libsilent_speech_hip.so')      # override: A/B runs of two builds on one box
 
 SS_F32, SS_BF16, SS_F64, SS_F32X3 = 0, 1, 2, 3
-ABI_VERSION = 13         # include/silent_speech_hip.h: SS_ABI_VERSION (struct layouts / signatures this binding was written against)
+ABI_VERSION = 14         # include/silent_speech_hip.h: SS_ABI_VERSION (struct layouts / signatures this binding was written against)
 OP_KC, OP_OC = 0, 1
 
 
@@ -49,6 +49,14 @@ class PermuteJob(ctypes.Structure):
                 ('valid1', ctypes.c_int32), ('valid2', ctypes.c_int32), ('in_dtype', ctypes.c_int32), ('out_dtype', ctypes.c_int32),
                 ('accumulate', ctypes.c_int32), ('scale', ctypes.c_float), ('first_block', ctypes.c_int32), ('nblocks', ctypes.c_int32),
                 ('pad_', ctypes.c_int32)]
+
+
+class WordLm(ctypes.Structure):
+    _fields_ = [('lex_child', ctypes.c_void_p), ('lex_word', ctypes.c_void_p), ('uni_logp', ctypes.c_void_p), ('uni_bo', ctypes.c_void_p),
+                ('bi_keys', ctypes.c_void_p), ('bi_logp', ctypes.c_void_p), ('bi_bo', ctypes.c_void_p), ('tri_keys', ctypes.c_void_p),
+                ('tri_logp', ctypes.c_void_p), ('n_nodes', ctypes.c_int32), ('n_vocab', ctypes.c_int32), ('n_uni', ctypes.c_int32),
+                ('start', ctypes.c_int32), ('bi_slots', ctypes.c_int32), ('bi_probe', ctypes.c_int32), ('tri_slots', ctypes.c_int32),
+                ('tri_probe', ctypes.c_int32)]
 
 
 _P, _I, _F, _L = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64
@@ -100,6 +108,8 @@ SIGNATURES = {
     'ss_phoneme_confusion': [_P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _P],
     'ss_ctc_loss': [_P, _L, _I, _I, _P, _P, _I, _I, _L, _P, _P, _P, _P, _P, _P, _P],
     'ss_ctc_beam_search': [_P, _L, _I, _I, _L, _P, _P, _I, _L, _I, _I, _P, _F, _F, _P, _I, _P, _P, _P, _P, _P],
+    'ss_ctc_word_beam_search': [_P, _L, _I, _I, _I, _L, _P, _P, _I, _L, _I, _I, ctypes.POINTER(WordLm), _F, _F, _P, _I, _P, _P, _P, _P, _P, _P],
+    'ss_word_ngram_score': [ctypes.POINTER(WordLm), _P, _L, _P, _P],
     'ss_adamw_step': [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _F, _P],
     'ss_cast_f32': [_P, _P, _I, _L, _P],
     'ss_soft_clip': [_P, _P, _L, _I, _P, _P, _F, _F, _P],
@@ -150,6 +160,7 @@ _HOST_FUNCS = {'ss_dtw_workspace_bytes': ([_I, _I, _LP, _LP, _LP], ctypes.c_int6
                'ss_relpos_attention_x3_table_bytes': ([_I, _I, _I], ctypes.c_int64),
                'ss_relpos_attention_saved_bytes': ([_I, _I, _I, _I, _I, _I], ctypes.c_int64),
                'ss_ctc_beam_workspace_bytes': ([_I, _L, _I], ctypes.c_int64),
+               'ss_ctc_word_beam_workspace_bytes': ([_I, _L, _I], ctypes.c_int64),
                'ss_voc_blob_bytes': ([_I, _I, _I], ctypes.c_int64),
                'ss_voc_workspace_bytes': ([_L, _I, ctypes.POINTER(ctypes.c_int), _I], ctypes.c_int64),
                'ss_voc_supported': ([_I, _I, _I, _I, _I], ctypes.c_int),

@@ -5,6 +5,8 @@
     beam_decode(logits, lengths, blank)      CTC prefix beam search on the device (csrc/ctc_decode.hip), optionally fused with a LabelNgramLM
     beam_decode_utterances(logits)           the same for the list Model.forward_utterances returns
     LabelNgramLM                             label trigram table counted from text, the language model of the beam search
+    WordNgramLM                              word n-gram with backoff (orders 1 .. 3, from ARPA text or counted from transcripts) + the lexicon of
+                                             its vocabulary: beam_decode* with it run the lexicon-constrained search of csrc/ctc_word_decode.hip
     test(model, testset, device)             :30-58 -> WER; decoder='greedy' (default) or 'beam'
     train_model(trainset, devset, device)    :61-117 (AdamW, warm-up, x2 gradient accumulation, MultiStepLR)
 
@@ -12,9 +14,11 @@ The encoder is the same MI355X engine as the transduction trainer (Model without
 alpha/beta recursion and its gradient run in csrc/ctc.hip straight on the packed (rows*200, V) logits, so the
 decollate + pad_sequence copies and the (T_max, N, V) log-prob tensor of the reference never exist.
 The search of the reference's decoder (ctcdecode, :33-35,48-49) is here as a kernel of its own: a prefix beam search over whole batches
-in one launch, with shallow fusion of a label n-gram table that lives on the device (LabelNgramLM).  Its KenLM WORD language model
-(third-party C++ plus an lm.binary file) stays out of scope, so parity with the reference's WER stays unpinned; test() reports greedy
-WER by default and beam-search WER with decoder='beam'.
+in one launch, with shallow fusion of a label n-gram table that lives on the device (LabelNgramLM), or -- as ctcdecode does it with a
+KenLM model -- confined to the spellings of a vocabulary with a WORD n-gram with backoff scored at every word end (WordNgramLM: orders 1 to 3,
+read from ARPA text or counted from transcripts; the search is lexicon-constrained, there is no out-of-vocabulary escape).  Out of scope: the
+KenLM BINARY format (third-party C++; convert lm.binary to ARPA text) and parity with ctcdecode's own numbers, which stays unpinned because
+ctcdecode is not available to compare against.  test() reports greedy WER by default and beam-search WER with decoder='beam'.
 """
 import logging
 import os
@@ -201,17 +205,325 @@ class LabelNgramLM(object):
         return LabelNgramLM(self.table.to(device))
 
 
-def _beam_search(head, V, blank, first, frames, beam_width, n_best, lm, alpha, beta):
-    """One table upload, lse + search launches, one read-back.  head: (M, ld) f32 on the device; first / frames: per utterance, host ints."""
+_NGRAM_EMPTY = np.uint64(0xFFFFFFFFFFFFFFFF)
+_LN10 = float(np.log(10.0))
+
+
+def _ngram_home(keys):
+    """Home slot (before masking with slots - 1) of packed n-gram keys: the low 32 bits of the splitmix64 finaliser of key + 0x9E3779B97F4A7C15,
+    as include/silent_speech_hip.h states it for ss_word_lm."""
+    x = np.asarray(keys, dtype=np.uint64).copy()
+    with np.errstate(over='ignore'):
+        x += np.uint64(0x9E3779B97F4A7C15)
+        x ^= x >> np.uint64(30)
+        x *= np.uint64(0xBF58476D1CE4E5B9)
+        x ^= x >> np.uint64(27)
+        x *= np.uint64(0x94D049BB133111EB)
+        x ^= x >> np.uint64(31)
+    return x & np.uint64(0xFFFFFFFF)
+
+
+def _ngram_table(keys, values, columns, min_slots):
+    """Open addressing, linear probing, load factor <= 0.5: (keys (slots) uint64 with all ones = empty, values (columns, slots) f32, longest
+    probe); no keys: no table (0 slots)."""
+    keys, values = np.asarray(keys, dtype=np.uint64), np.asarray(values, dtype=np.float32).reshape(len(keys), columns)
+    if len(keys) == 0:
+        return np.zeros(0, dtype=np.uint64), np.zeros((columns, 0), dtype=np.float32), 0
+    slots = 1
+    while slots < max(2 * len(keys), int(min_slots)):
+        slots *= 2
+    tab, val, probe = np.full(slots, _NGRAM_EMPTY, dtype=np.uint64), np.zeros((values.shape[1], slots), dtype=np.float32), 0
+    home = (_ngram_home(keys) & np.uint64(slots - 1)).astype(np.int64)
+    for i in np.argsort(keys, kind='stable'):
+        s, n = int(home[i]), 1
+        while tab[s] != _NGRAM_EMPTY:
+            s, n = (s + 1) & (slots - 1), n + 1
+        tab[s], val[:, s], probe = keys[i], values[i], max(probe, n)
+    return tab, val, probe
+
+
+class WordNgramLM(object):
+    """Word n-gram with backoff of order 1 to 3 and the lexicon trie of its vocabulary: the language model of the lexicon-constrained beam search
+    (include/silent_speech_hip.h: ss_word_lm, ss_ctc_word_beam_search).  Natural log, f32.
+
+    words        the vocabulary, cleaned spellings over `chars`; word id = index, the start context <s> has id n_words
+    unigrams     (n_words + 1, 2) [ln P(w), backoff of the context (w)]
+    bigrams      {(w1, w): (ln P(w | w1), backoff of the context (w1, w))},  trigrams {(w2, w1, w): ln P(w | w2, w1)}
+    chars        the labels of the text transform; label number = index (the CTC classes with the blank skipped)
+    min_slots    least slot count of each hash table (tests force wrap-around and long probes with it)
+
+    Device form (torch tensors, `to(device)`): lex_child (n_nodes, C) / lex_word (n_nodes) int32, uni (2, n_words + 1) f32, bi_keys (slots) int64 +
+    bi_val (2, slots) f32, tri_keys (slots) int64 + tri_val (slots) f32, bi_probe / tri_probe = the longest probe sequence of each table."""
+    MAX_WORDS = 1 << 21
+
+    def __init__(self, words, unigrams, bigrams, trigrams, chars, min_slots=0):
+        words = [str(w) for w in words]
+        n = len(words)
+        uni = np.asarray(unigrams, dtype=np.float32).reshape(-1, 2)
+        if n + 1 > self.MAX_WORDS or uni.shape[0] != n + 1:
+            raise ValueError('WordNgramLM: %d words (< 2^21) need %d unigram rows, the last one the start context' % (n, n + 1))
+        if len(set(words)) != n or any(not w or any(c == ' ' or c not in chars for c in w) for w in words):
+            raise ValueError('WordNgramLM: the words must be distinct, non-empty and spelled with the labels %r without the space' % (chars,))
+        self.words, self.chars, self.min_slots = words, str(chars), int(min_slots)
+        self.unigrams = uni
+        self.bigrams = {(int(a), int(b)): (np.float32(v[0]), np.float32(v[1])) for (a, b), v in (bigrams or {}).items()}
+        self.trigrams = {(int(a), int(b), int(c)): np.float32(v) for (a, b, c), v in (trigrams or {}).items()}
+        if any(not (0 <= a <= n and 0 <= b < n) for a, b in self.bigrams) or any(not (0 <= a <= n and 0 <= b < n and 0 <= c < n) for a, b, c in self.trigrams):
+            raise ValueError('WordNgramLM: n-gram word ids must be below %d (the start context %d only leads)' % (n, n))
+        # the lexicon trie
+        C = len(self.chars)
+        child, word = [[-1] * C], [-1]
+        for w, spelling in enumerate(words):
+            node = 0
+            for ch in spelling:
+                c = self.chars.index(ch)
+                if child[node][c] < 0:
+                    child[node][c] = len(child)
+                    child.append([-1] * C)
+                    word.append(-1)
+                node = child[node][c]
+            word[node] = w
+        self.lex_child = torch.from_numpy(np.asarray(child, dtype=np.int32).reshape(len(child), C))
+        self.lex_word = torch.from_numpy(np.asarray(word, dtype=np.int32))
+        # the hash tables
+        bk = sorted(self.bigrams)
+        tk = sorted(self.trigrams)
+        bkeys = np.asarray([(a << 21) | b for a, b in bk], dtype=np.uint64)
+        tkeys = np.asarray([(a << 42) | (b << 21) | c for a, b, c in tk], dtype=np.uint64)
+        btab, bval, self.bi_probe = _ngram_table(bkeys, [self.bigrams[k] for k in bk], 2, min_slots)
+        ttab, tval, self.tri_probe = _ngram_table(tkeys, [self.trigrams[k] for k in tk], 1, min_slots)
+        self.uni = torch.from_numpy(np.ascontiguousarray(uni.T))
+        self.bi_keys, self.bi_val = torch.from_numpy(btab.view(np.int64)), torch.from_numpy(bval)
+        self.tri_keys, self.tri_val = torch.from_numpy(ttab.view(np.int64)), torch.from_numpy(tval.reshape(-1))
+
+    _DEVICE_FORM = ('lex_child', 'lex_word', 'uni', 'bi_keys', 'bi_val', 'tri_keys', 'tri_val')
+
+    @property
+    def n_words(self):
+        return len(self.words)
+
+    @property
+    def start(self):
+        return len(self.words)
+
+    @property
+    def order(self):
+        return 3 if self.trigrams else 2 if self.bigrams else 1
+
+    def to(self, device):
+        """The same model with its tables on `device` (the host form is shared, not copied)."""
+        other = object.__new__(WordNgramLM)
+        other.__dict__.update(self.__dict__)
+        for name in self._DEVICE_FORM:
+            setattr(other, name, getattr(self, name).to(device))
+        return other
+
+    def word_ids(self, text, text_transform):
+        """Ids of the words of `text` after clean_text; raises KeyError on a word outside the vocabulary."""
+        index = getattr(self, '_index', None)
+        if index is None:
+            index = self._index = {w: i for i, w in enumerate(self.words)}
+        return [index[w] for w in text_transform.clean_text(text).split()]
+
+    def score_words(self, word_ids, dtype=np.float64, context=None):
+        """ln P of every word of a sentence given the words before it -- the backoff rule of ss_word_lm restated on the host tables, in `dtype`
+        arithmetic: tri(w2, w1, w) if present; else (backoff of bi(w2, w1), 0 if absent) + P2, P2 = bi(w1, w) if present, else backoff(w1) +
+        uni(w); with w2 = none (-1), P2.  context = (w2, w1) the sentence starts in; default (none, <s>)."""
+        w2, w1 = (-1, self.start) if context is None else (int(context[0]), int(context[1]))
+        out = np.zeros(len(word_ids), dtype=dtype)
+        for i, w in enumerate(word_ids):
+            w = int(w)
+            if not (0 <= w <= self.n_words) or not (-1 <= w1 <= self.n_words) or not (-1 <= w2 <= self.n_words):
+                raise ValueError('score_words: word id outside the model')
+            if w1 < 0:
+                p = dtype(self.unigrams[w, 0])
+            elif w2 >= 0 and (w2, w1, w) in self.trigrams:
+                p = dtype(self.trigrams[(w2, w1, w)])
+            else:
+                p = dtype(self.bigrams[(w1, w)][0]) if (w1, w) in self.bigrams else dtype(self.unigrams[w1, 1]) + dtype(self.unigrams[w, 0])
+                if w2 >= 0 and (w2, w1) in self.bigrams:
+                    p = dtype(self.bigrams[(w2, w1)][1]) + p
+            out[i] = p
+            w2, w1 = w1, w
+        return out
+
+    def score_triples(self, triples):
+        """torch.ops.silent_speech.word_ngram_score on this model's tables: ln P(w | w2, w1) of (n, 3) int32 rows (w2, w1, w) on the tables' device."""
+        return torch.ops.silent_speech.word_ngram_score(triples, self.uni, self.bi_keys, self.bi_val, self.tri_keys, self.tri_val, self.bi_probe, self.tri_probe)
+
+    # ---- builders
+    @classmethod
+    def from_arpa(cls, path_or_file, text_transform, min_slots=0):
+        """Reads ARPA text (\\data\\, \\1-grams: .. \\3-grams:, \\end\\; log10 values, a missing backoff = 0).  <s> is the start context; </s> and
+        <unk> are read and never predicted (the search is lexicon-constrained, so n-grams holding them can never be asked for and are left out).
+        A word whose clean_text spelling is empty, holds a space or a character outside text_transform.chars is dropped with every n-gram
+        holding it; of two words with one cleaned spelling the one with the larger unigram probability keeps it.  Order > 3: ValueError."""
+        f = open(path_or_file) if isinstance(path_or_file, (str, os.PathLike)) else path_or_file
+        try:
+            lines = [line.strip() for line in f]
+        finally:
+            if f is not path_or_file:
+                f.close()
+        grams, order = {1: [], 2: [], 3: []}, 0
+        for line in lines:
+            if not line or line == '\\data\\':
+                continue
+            if line == '\\end\\':
+                break
+            if line.startswith('ngram '):
+                n, count = line[6:].split('=')
+                if int(n) > 3 and int(count) > 0:
+                    raise ValueError('WordNgramLM.from_arpa: order %d (orders 1 to 3 are supported)' % int(n))
+                continue
+            if line.startswith('\\') and line.endswith('-grams:'):
+                order = int(line[1:-7])
+                if order > 3:
+                    raise ValueError('WordNgramLM.from_arpa: order %d (orders 1 to 3 are supported)' % order)
+                continue
+            if order == 0:
+                continue
+            f_ = line.split()
+            if len(f_) not in (order + 1, order + 2):
+                raise ValueError('WordNgramLM.from_arpa: cannot read %r as a %d-gram' % (line, order))
+            grams[order].append((tuple(f_[1:order + 1]), float(f_[0]) * _LN10, float(f_[order + 1]) * _LN10 if len(f_) == order + 2 else 0.0))
+        chars = text_transform.chars
+        best = {}                                                            # cleaned spelling -> (unigram ln P, ARPA word)
+        for (w,), lp, _ in grams[1]:
+            if w in ('<s>', '</s>', '<unk>'):
+                continue
+            sp = text_transform.clean_text(w)
+            if sp and all(c != ' ' and c in chars for c in sp) and (sp not in best or lp > best[sp][0]):
+                best[sp] = (lp, w)
+        words = sorted(best)
+        ids = {best[sp][1]: i for i, sp in enumerate(words)}
+        ids['<s>'] = len(words)
+        uni = np.zeros((len(words) + 1, 2), dtype=np.float64)
+        uni[len(words), 0] = -99.0 * _LN10
+        for (w,), lp, bo in grams[1]:
+            if w in ids:
+                uni[ids[w]] = (lp, bo)
+        bi = {(ids[a], ids[b]): (lp, bo) for (a, b), lp, bo in grams[2] if a in ids and b in ids and b != '<s>'}
+        tri = {(ids[a], ids[b], ids[c]): lp for (a, b, c), lp, _ in grams[3] if a in ids and b in ids and c in ids and b != '<s>' and c != '<s>'}
+        return cls(words, uni, bi, tri, chars, min_slots)
+
+    @classmethod
+    def from_texts(cls, texts, text_transform, order=3, discount=0.75, add_k=0.1, min_slots=0):
+        """Counts word n-grams over the cleaned texts, each starting in the <s> context.  Unigrams: add-k over the vocabulary,
+        P(w) = (c(w) + add_k) / (N + add_k n_words).  Seen bigrams and trigrams: absolute discounting, P(w | h) = (c(h w) - discount) / c(h .),
+        and the backoff weight of every seen context gives the rest to the lower order so that the probabilities over the vocabulary sum to 1:
+        bo(h) = (1 - sum_seen P(w | h)) / (1 - sum_seen P_lower(w | h')).  (A context after which EVERY word of the vocabulary was seen keeps
+        its undiscounted relative frequencies.)  Words that clean_text cannot spell with text_transform.chars are skipped with the n-grams
+        holding them."""
+        if order not in (1, 2, 3) or not (0 < discount < 1) or not add_k > 0:
+            raise ValueError('WordNgramLM.from_texts: order 1, 2 or 3, 0 < discount < 1 and add_k > 0')
+        chars = text_transform.chars
+        sents = [[w if all(c in chars for c in w) else None for w in text_transform.clean_text(t).split()] for t in texts]
+        words = sorted({w for s in sents for w in s if w is not None})
+        n, ids = len(words), {}
+        ids.update({w: i for i, w in enumerate(words)})
+        c1, c2, c3 = np.zeros(n, dtype=np.float64), {}, {}
+        for s in sents:
+            seq = [n] + [ids[w] if w is not None else None for w in s]
+            for i in range(1, len(seq)):
+                if seq[i] is None:
+                    continue
+                c1[seq[i]] += 1
+                if order >= 2 and seq[i - 1] is not None:
+                    c2[(seq[i - 1], seq[i])] = c2.get((seq[i - 1], seq[i]), 0) + 1
+                    if order >= 3 and i >= 2 and seq[i - 2] is not None:
+                        k = (seq[i - 2], seq[i - 1], seq[i])
+                        c3[k] = c3.get(k, 0) + 1
+        p1 = (c1 + add_k) / (c1.sum() + add_k * max(n, 1))
+        uni = np.zeros((n + 1, 2), dtype=np.float64)
+        uni[:n, 0] = np.log(p1)
+        uni[n, 0] = -99.0 * _LN10
+
+        def discounted(counts, lower):
+            """{context: {w: P}} and {context: ln backoff} from {(context..., w): count}; lower(context, w) = the lower order's P."""
+            by = {}
+            for k, c in counts.items():
+                by.setdefault(k[:-1], {})[k[-1]] = c
+            P, BO = {}, {}
+            for h, cs in by.items():
+                total = float(sum(cs.values()))
+                rest = 1.0 - sum(lower(h, w) for w in cs)
+                if len(cs) == n or rest <= 1e-12:
+                    P[h], BO[h] = {w: c / total for w, c in cs.items()}, 0.0
+                else:
+                    P[h] = {w: (c - discount) / total for w, c in cs.items()}
+                    BO[h] = float(np.log((1.0 - sum(P[h].values())) / rest))
+            return P, BO
+        P2, BO1 = discounted(c2, lambda h, w: p1[w])
+        for (w1,), bo in BO1.items():
+            uni[w1, 1] = bo
+
+        def p_bi(w1, w):
+            return P2[(w1,)][w] if (w1,) in P2 and w in P2[(w1,)] else float(np.exp(uni[w1, 1])) * p1[w]
+        P3, BO2 = discounted(c3, lambda h, w: p_bi(h[1], w))
+        bi = {(w1, w): (float(np.log(p)), BO2.get((w1, w), 0.0)) for (w1,), ps in P2.items() for w, p in ps.items()}
+        tri = {(w2, w1, w): float(np.log(p)) for (w2, w1), ps in P3.items() for w, p in ps.items()}
+        return cls(words, uni, bi, tri, chars, min_slots)
+
+    def write_arpa(self, path):
+        """ARPA text of the model (log10 values; the words as their cleaned spellings), readable by from_arpa and by other n-gram tools."""
+        n = self.n_words
+        name = self.words + ['<s>']
+        with open(path, 'w') as f:
+            f.write('\\data\\\nngram 1=%d\n' % (n + 1))
+            if self.bigrams:
+                f.write('ngram 2=%d\n' % len(self.bigrams))
+            if self.trigrams:
+                f.write('ngram 3=%d\n' % len(self.trigrams))
+            f.write('\n\\1-grams:\n')
+            for w in range(n + 1):
+                f.write('%.9g\t%s\t%.9g\n' % (float(self.unigrams[w, 0]) / _LN10, name[w], float(self.unigrams[w, 1]) / _LN10))
+            if self.bigrams:
+                f.write('\n\\2-grams:\n')
+                for (a, b) in sorted(self.bigrams):
+                    lp, bo = self.bigrams[(a, b)]
+                    f.write('%.9g\t%s %s\t%.9g\n' % (float(lp) / _LN10, name[a], name[b], float(bo) / _LN10))
+            if self.trigrams:
+                f.write('\n\\3-grams:\n')
+                for (a, b, c) in sorted(self.trigrams):
+                    f.write('%.9g\t%s %s %s\n' % (float(self.trigrams[(a, b, c)]) / _LN10, name[a], name[b], name[c]))
+            f.write('\n\\end\\\n')
+
+    def save(self, path):
+        bk, tk = sorted(self.bigrams), sorted(self.trigrams)
+        with open(path, 'wb') as f:
+            np.savez(f, words=np.asarray(self.words, dtype=np.str_), chars=np.asarray(self.chars), unigrams=self.unigrams, min_slots=np.asarray(self.min_slots),
+                     bi_ids=np.asarray(bk, dtype=np.int32).reshape(len(bk), 2), bi_val=np.asarray([self.bigrams[k] for k in bk], dtype=np.float32).reshape(len(bk), 2),
+                     tri_ids=np.asarray(tk, dtype=np.int32).reshape(len(tk), 3), tri_val=np.asarray([self.trigrams[k] for k in tk], dtype=np.float32))
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path) as z:
+            bi = {tuple(k): tuple(v) for k, v in zip(z['bi_ids'].tolist(), z['bi_val'])}
+            tri = {tuple(k): v for k, v in zip(z['tri_ids'].tolist(), z['tri_val'])}
+            return cls([str(w) for w in z['words']], z['unigrams'], bi, tri, str(z['chars']), int(z['min_slots']))
+
+
+def _beam_search(head, V, blank, first, frames, beam_width, n_best, lm, alpha, beta, space=None):
+    """One table upload, lse + search launches, one read-back.  head: (M, ld) f32 on the device; first / frames: per utterance, host ints.
+    A WordNgramLM selects the lexicon-constrained search (space: the class that ends a word, default V - 2)."""
     n = len(frames)
     if n == 0:
         return []
-    if lm is not None:
-        lm = (lm.table if isinstance(lm, LabelNgramLM) else torch.as_tensor(lm, dtype=torch.float32)).to(head.device).contiguous()
     utt, = staging.upload([np.stack([np.asarray(first, dtype=np.int64), np.asarray(frames, dtype=np.int64)], 1)], head.device)
     max_len = max(max(frames), 1)
-    labels, lengths, scores, _ = torch.ops.silent_speech.ctc_beam_search(head, utt, V, blank, int(sum(frames)), max_len, int(beam_width), int(n_best),
-                                                                         lm, float(alpha), float(beta))
+    if isinstance(lm, WordNgramLM):
+        if len(lm.chars) != V - 1:
+            raise ValueError('beam search: the WordNgramLM spells with %d labels, the logits have %d classes' % (len(lm.chars), V))
+        space = V - 2 if space is None else int(space)
+        lm = lm.to(head.device)
+        labels, lengths, scores, _, _ = torch.ops.silent_speech.ctc_word_beam_search(
+            head, utt, V, blank, space, int(sum(frames)), max_len, int(beam_width), int(n_best), lm.lex_child, lm.lex_word, lm.uni, lm.bi_keys, lm.bi_val,
+            lm.tri_keys, lm.tri_val, lm.n_words, lm.start, lm.bi_probe, lm.tri_probe, float(alpha), float(beta))
+    else:
+        if lm is not None:
+            lm = (lm.table if isinstance(lm, LabelNgramLM) else torch.as_tensor(lm, dtype=torch.float32)).to(head.device).contiguous()
+        labels, lengths, scores, _ = torch.ops.silent_speech.ctc_beam_search(head, utt, V, blank, int(sum(frames)), max_len, int(beam_width), int(n_best),
+                                                                             lm, float(alpha), float(beta))
     back = torch.cat([labels.reshape(n, n_best * max_len), lengths, scores.view(torch.int32)], 1).cpu().numpy()       # ONE read-back
     labels, lengths = back[:, :n_best * max_len].reshape(n, n_best, max_len), back[:, n_best * max_len:n_best * max_len + n_best]
     scores = np.ascontiguousarray(back[:, n_best * max_len + n_best:]).view(np.float32)
@@ -220,10 +532,13 @@ def _beam_search(head, V, blank, first, frames, beam_width, n_best, lm, alpha, b
     return [[(labels[b, r, :lengths[b, r]].tolist(), float(scores[b, r])) for r in range(n_best) if lengths[b, r] >= 0] for b in range(n)]
 
 
-def beam_decode(pred, lengths, blank=None, *, beam_width=100, n_best=1, lm=None, alpha=0.0, beta=0.0):
+def beam_decode(pred, lengths, blank=None, *, beam_width=100, n_best=1, lm=None, alpha=0.0, beta=0.0, space=None):
     """CTC prefix beam search of packed logits (rows, T, V) (NOT log-softmaxed), utterances back to back with `lengths` frames each, in one
-    launch on the device; lm: a LabelNgramLM (or its table) fused as alpha * ln P(label | two labels before) + beta per label.
-    Returns a list of int lists, or for n_best > 1 a list of [(ints, score), ...] lists, best first (fewer than n_best if fewer prefixes exist)."""
+    launch on the device; lm: a LabelNgramLM (or its table) fused as alpha * ln P(label | two labels before) + beta per label, or a WordNgramLM:
+    the search is then confined to the spellings of its vocabulary and adds alpha * ln P(word | two words before) + beta per word; space = the
+    class that ends a word (default V - 2, where TextTransform puts it; pass text_transform.chars.index(' ')).
+    Returns a list of int lists, or for n_best > 1 a list of [(ints, score), ...] lists, best first (fewer than n_best if fewer prefixes exist;
+    with a WordNgramLM the strings that end at a word boundary or on a word come first)."""
     B, T, V = pred.shape
     blank = V - 1 if blank is None else int(blank)
     logits = pred.reshape(B * T, V).float().contiguous()
@@ -231,10 +546,10 @@ def beam_decode(pred, lengths, blank=None, *, beam_width=100, n_best=1, lm=None,
     if sum(frames) > B * T or any(n < 0 for n in frames):
         raise ValueError('beam_decode: the lengths do not fit the %d packed frames' % (B * T))
     first = np.concatenate([[0], np.cumsum(frames)])[:-1] if frames else []
-    return _beam_search(logits, V, blank, first, frames, beam_width, n_best, lm, alpha, beta)
+    return _beam_search(logits, V, blank, first, frames, beam_width, n_best, lm, alpha, beta, space)
 
 
-def beam_decode_utterances(logits, *, beam_width=100, n_best=1, lm=None, alpha=0.0, beta=0.0):
+def beam_decode_utterances(logits, *, beam_width=100, n_best=1, lm=None, alpha=0.0, beta=0.0, space=None):
     """beam_decode for the per-utterance logits Model.forward_utterances returns -- (T_b, V) views of ONE (B T_max, >= V) head buffer --: the
     search reads the slots in place (first frame b T_max, T_b frames; filler rows and columns are never looked at).  blank = V - 1."""
     if not logits:
@@ -244,7 +559,7 @@ def beam_decode_utterances(logits, *, beam_width=100, n_best=1, lm=None, alpha=0
     if head is None or head.dim() != 2 or head.dtype != torch.float32 or not head.is_contiguous() or head.shape[0] != B * T or \
             any(y._base is not head or y.shape[1] != V or y.storage_offset() != b * T * head.shape[1] for b, y in enumerate(logits)):
         raise ValueError('beam_decode_utterances takes the list Model.forward_utterances returned')
-    return _beam_search(head, V, V - 1, [b * T for b in range(B)], [int(y.shape[0]) for y in logits], beam_width, n_best, lm, alpha, beta)
+    return _beam_search(head, V, V - 1, [b * T for b in range(B)], [int(y.shape[0]) for y in logits], beam_width, n_best, lm, alpha, beta, space)
 
 
 def test(model, testset, device, *, batch_size=1, whole_utterances=False, decoder='greedy', beam_width=100, lm=None, alpha=0.0, beta=0.0):
@@ -255,15 +570,21 @@ def test(model, testset, device, *, batch_size=1, whole_utterances=False, decode
     plan call per group, every utterance computed as it is alone) and one arg-max launch + one read-back per group: the function of the
     default, at batched speed.
     decoder='greedy' (default): best-path decoding.  decoder='beam': the prefix beam search of beam_decode / beam_decode_utterances with
-    beam_width, and lm / alpha / beta if a LabelNgramLM is given, in all three branches (the reference's KenLM word model is out of scope)."""
+    beam_width, and lm / alpha / beta if a LabelNgramLM or a WordNgramLM is given, in all three branches.  With a WordNgramLM (the reference's
+    setting is alpha=1.5, beta=1.85) every predicted word is a word of its lexicon; ONE language model at a time: a LabelNgramLM and a
+    WordNgramLM together (lm given as a list or tuple) raise ValueError."""
     if decoder not in ('greedy', 'beam'):
         raise ValueError("test: decoder is 'greedy' or 'beam'")
+    if isinstance(lm, (list, tuple)):
+        raise ValueError('test: one language model at a time -- a LabelNgramLM and a WordNgramLM cannot be combined')
     model.eval()
     tt = testset.text_transform
     blank = len(tt.chars)
     if decoder == 'beam':
-        lm = lm.to(device) if isinstance(lm, LabelNgramLM) else lm                  # the table crosses to the device once, not per utterance
+        lm = lm.to(device) if isinstance(lm, (LabelNgramLM, WordNgramLM)) else lm   # the tables cross to the device once, not per utterance
         search = dict(beam_width=beam_width, lm=lm, alpha=alpha, beta=beta)
+        if isinstance(lm, WordNgramLM):
+            search['space'] = tt.chars.index(' ')
         decode = lambda pred, lengths: beam_decode(pred, lengths, blank, **search)
         decode_utterances = lambda logits: beam_decode_utterances(logits, **search)
     else:

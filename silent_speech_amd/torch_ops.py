@@ -6,6 +6,8 @@
     dtw_align                        align.py:16-34 on one device matrix
     ctc_loss                         recognition_model.py:96-101
     ctc_beam_search                  the search of recognition_model.py:33-35,48-49: CTC prefix beam search + label n-gram table, one launch per batch (inference only)
+    ctc_word_beam_search             the same search confined to a lexicon, a word n-gram with backoff scored at every word end (WordNgramLM), inference only
+    word_ngram_score                 ln P(w | w2, w1) of word triples by the device function of that search (tests, n-best rescoring)
     stft_logmel                      data_utils.py:39-62
     emg_features                     data_utils.py:85-136 (get_emg_features; no autograd: the reference's features are numpy)
     fused_adamw                      torch.optim.AdamW over the flat parameter arena (transduction_model.py:178,210)
@@ -17,6 +19,7 @@ and, where the reference differentiates through it, a registered autograd formul
 tensors and plain scalars only; per-model state (bound plan, weight copies) is looked up through an integer handle.
 Emulator builds (tests) run the same registrations on CPU tensors.
 """
+import ctypes
 import weakref
 from typing import Optional, Tuple
 
@@ -287,6 +290,109 @@ def _(logits, utt, V, blank, total_frames, max_len, beam_width, n_best, lm, alph
             logits.new_empty((n, n_best)), logits.new_empty((n, n_best)))
 
 
+# ------------------------------------------------------------------------------------------------ ctc_word_beam_search / word_ngram_score (inference only)
+def _word_tables(name, dev, uni, bi_keys, bi_val, tri_keys, tri_val, bi_probe, tri_probe):
+    """Checks the n-gram tables of a WordNgramLM (ss_word_lm in include/silent_speech_hip.h) and fills the part of the struct they make up."""
+    def bad(t, dtype, dim):
+        return t.dtype != dtype or t.dim() != dim or not t.is_contiguous() or t.device != dev
+    if bad(uni, torch.float32, 2) or uni.shape[0] != 2 or not (1 <= uni.shape[1] <= 1 << 21):
+        raise RuntimeError('%s: the unigram table must be a contiguous (2, n <= 2^21) float32 tensor on the device of the input' % name)
+    nb, nt = bi_keys.shape[0] if bi_keys.dim() == 1 else -1, tri_keys.shape[0] if tri_keys.dim() == 1 else -1
+    if bad(bi_keys, torch.int64, 1) or bad(bi_val, torch.float32, 2) or tuple(bi_val.shape) != (2, nb) or nb & (nb - 1) or not (0 <= bi_probe <= nb):
+        raise RuntimeError('%s: the bigram table must be int64 keys (slots) and float32 values (2, slots) on the device of the input, '
+                           'slots 0 or a power of two, longest probe within them' % name)
+    if bad(tri_keys, torch.int64, 1) or bad(tri_val, torch.float32, 1) or tri_val.shape[0] != nt or nt & (nt - 1) or not (0 <= tri_probe <= nt):
+        raise RuntimeError('%s: the trigram table must be int64 keys (slots) and float32 values (slots) on the device of the input, '
+                           'slots 0 or a power of two, longest probe within them' % name)
+    n_uni = uni.shape[1]
+    lm = _lib.WordLm()
+    lm.uni_logp, lm.uni_bo = uni.data_ptr(), uni.data_ptr() + 4 * n_uni
+    lm.bi_keys, lm.bi_logp, lm.bi_bo = (bi_keys.data_ptr(), bi_val.data_ptr(), bi_val.data_ptr() + 4 * nb) if nb else (None, None, None)
+    lm.tri_keys, lm.tri_logp = (tri_keys.data_ptr(), tri_val.data_ptr()) if nt else (None, None)
+    lm.n_uni, lm.n_vocab, lm.start, lm.n_nodes = n_uni, n_uni, 0, 0
+    lm.bi_slots, lm.bi_probe, lm.tri_slots, lm.tri_probe = nb, bi_probe, nt, tri_probe
+    _p(uni)                                                              # (the one place that refuses memory the kernels cannot read)
+    return lm
+
+
+@torch.library.custom_op('silent_speech::ctc_word_beam_search', mutates_args=())
+def ctc_word_beam_search(logits: Tensor, utt: Tensor, V: int, blank: int, space: int, total_frames: int, max_len: int, beam_width: int, n_best: int,
+                         lex_child: Tensor, lex_word: Tensor, uni: Tensor, bi_keys: Tensor, bi_val: Tensor, tri_keys: Tensor, tri_val: Tensor,
+                         n_vocab: int, start: int, bi_probe: int, tri_probe: int, alpha: float, beta: float) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """Lexicon-constrained CTC prefix beam search with a word n-gram (ss_ctc_word_beam_search in include/silent_speech_hip.h states the algorithm).
+    logits, utt, V, blank, total_frames, max_len, beam_width, n_best as for ctc_beam_search; space: the class that ends a word.  The tables are
+    the device form of recognition_model.WordNgramLM: lex_child [n_nodes][V - 1] int32, lex_word [n_nodes] int32, uni [2][n_uni] f32 (ln P, backoff),
+    bi_keys [slots] int64 + bi_val [2][slots] f32, tri_keys [slots] int64 + tri_val [slots] f32, the word ids 0 .. n_vocab - 1 of the lexicon, the
+    id of the start context and the longest probe sequence of each hash table.
+    Returns (labels, lengths, scores, CTC scores) as ctc_beam_search and complete [n][n_best] int32 (1 / 0; -1: no such rank)."""
+    dev = logits.device
+    if logits.dim() != 2 or logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise RuntimeError('ctc_word_beam_search: logits must be a contiguous (frames, ld) float32 matrix')
+    if utt.dim() != 2 or utt.shape[1] != 2 or utt.dtype != torch.int64 or not utt.is_contiguous() or utt.device != dev:
+        raise RuntimeError('ctc_word_beam_search: utt must be a contiguous (n, 2) int64 table on the device of the logits')
+    if not (2 <= V <= min(logits.shape[1], 128)) or not (0 <= blank < V):
+        raise RuntimeError('ctc_word_beam_search: %d classes (2 .. min(row stride %d, 128)), blank %d' % (V, logits.shape[1], blank))
+    if not (0 <= space < V) or space == blank:
+        raise RuntimeError('ctc_word_beam_search: space class %d (0 .. %d, not the blank %d)' % (space, V - 1, blank))
+    if not (1 <= beam_width <= 128) or not (1 <= n_best <= beam_width):
+        raise RuntimeError('ctc_word_beam_search: beam width %d (1 .. 128), n_best %d (1 .. beam width)' % (beam_width, n_best))
+    if max_len < 1 or total_frames < 0:
+        raise RuntimeError('ctc_word_beam_search: max_len %d, total_frames %d' % (max_len, total_frames))
+    if lex_child.dim() != 2 or lex_child.shape[0] < 1 or lex_child.shape[1] != V - 1 or lex_child.dtype != torch.int32 or not lex_child.is_contiguous() or \
+            lex_child.device != dev or tuple(lex_word.shape) != (lex_child.shape[0],) or lex_word.dtype != torch.int32 or not lex_word.is_contiguous() or lex_word.device != dev:
+        raise RuntimeError('ctc_word_beam_search: the lexicon must be contiguous int32 tensors (n_nodes >= 1, %d) and (n_nodes) on the device of the logits' % (V - 1))
+    lm = _word_tables('ctc_word_beam_search', dev, uni, bi_keys, bi_val, tri_keys, tri_val, bi_probe, tri_probe)
+    if not (0 <= n_vocab <= lm.n_uni) or not (0 <= start < lm.n_uni):
+        raise RuntimeError('ctc_word_beam_search: %d words, start id %d, but %d word ids' % (n_vocab, start, lm.n_uni))
+    lm.lex_child, lm.lex_word, lm.n_nodes, lm.n_vocab, lm.start = lex_child.data_ptr(), lex_word.data_ptr(), lex_child.shape[0], n_vocab, start
+    M, ld = logits.shape
+    n = utt.shape[0]
+    st = _lib.stream_of(logits)
+    ws_bytes = _L().ss_ctc_word_beam_workspace_bytes(n, total_frames, beam_width)
+    if ws_bytes < 0:
+        raise RuntimeError('ctc_word_beam_search: beam width %d (1 .. 128)' % beam_width)
+    lse = torch.empty(max(M, 1), dtype=torch.float32, device=dev)
+    amax = torch.empty(max(M, 1), dtype=torch.int32, device=dev)
+    if M:
+        _lib.check(_L().ss_frame_lse(_p(logits), ld, 0, V, M, _p(lse), _p(amax), st), 'ss_frame_lse')
+    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
+    labels = torch.empty((n, n_best, max_len), dtype=torch.int32, device=dev)
+    lengths = torch.empty((n, n_best), dtype=torch.int32, device=dev)
+    scores = torch.empty((n, n_best), dtype=torch.float32, device=dev)
+    ctc_scores = torch.empty((n, n_best), dtype=torch.float32, device=dev)
+    complete = torch.empty((n, n_best), dtype=torch.int32, device=dev)
+    _lib.check(_L().ss_ctc_word_beam_search(_p(logits), ld, V, blank, space, M, _p(lse), _p(utt) if n else None, n, total_frames, beam_width, n_best,
+                                            ctypes.byref(lm), alpha, beta, _p(ws), max_len, _p(labels), _p(lengths), _p(scores), _p(ctc_scores),
+                                            _p(complete), st), 'ss_ctc_word_beam_search')
+    return labels, lengths, scores, ctc_scores, complete
+
+
+@ctc_word_beam_search.register_fake
+def _(logits, utt, V, blank, space, total_frames, max_len, beam_width, n_best, lex_child, lex_word, uni, bi_keys, bi_val, tri_keys, tri_val,
+      n_vocab, start, bi_probe, tri_probe, alpha, beta):
+    n = utt.shape[0]
+    return (logits.new_empty((n, n_best, max_len), dtype=torch.int32), logits.new_empty((n, n_best), dtype=torch.int32),
+            logits.new_empty((n, n_best)), logits.new_empty((n, n_best)), logits.new_empty((n, n_best), dtype=torch.int32))
+
+
+@torch.library.custom_op('silent_speech::word_ngram_score', mutates_args=())
+def word_ngram_score(triples: Tensor, uni: Tensor, bi_keys: Tensor, bi_val: Tensor, tri_keys: Tensor, tri_val: Tensor, bi_probe: int, tri_probe: int) -> Tensor:
+    """ln P(w | w2, w1) of every row (w2, w1, w) of triples [n][3] int32 (-1 = no such context word) by the backoff rule of ss_word_lm, with the
+    device function the word beam search uses.  An id outside the tables gives NaN.  Returns [n] f32."""
+    dev = triples.device
+    if triples.dim() != 2 or triples.shape[1] != 3 or triples.dtype != torch.int32 or not triples.is_contiguous():
+        raise RuntimeError('word_ngram_score: triples must be a contiguous (n, 3) int32 tensor')
+    lm = _word_tables('word_ngram_score', dev, uni, bi_keys, bi_val, tri_keys, tri_val, bi_probe, tri_probe)
+    out = torch.empty(triples.shape[0], dtype=torch.float32, device=dev)
+    _lib.check(_L().ss_word_ngram_score(ctypes.byref(lm), _p(triples), triples.shape[0], _p(out), _lib.stream_of(triples)), 'ss_word_ngram_score')
+    return out
+
+
+@word_ngram_score.register_fake
+def _(triples, uni, bi_keys, bi_val, tri_keys, tri_val, bi_probe, tri_probe):
+    return triples.new_empty((triples.shape[0],), dtype=torch.float32)
+
+
 # ------------------------------------------------------------------------------------------------ stft_logmel
 @torch.library.custom_op('silent_speech::stft_logmel', mutates_args=())
 def stft_logmel(y: Tensor, n_fft: int, num_mels: int, sampling_rate: int, hop_size: int, win_size: int, fmin: int, fmax: int, center: bool) -> Tensor:
@@ -387,5 +493,5 @@ def _(x, w, k, slope):
     return x.new_empty((x.shape[0],))
 
 
-OPS = ('model_forward', 'model_forward_ragged', 'model_backward', 'dtw_loss', 'dtw_align', 'ctc_loss', 'ctc_beam_search', 'stft_logmel', 'emg_features', 'fused_adamw',
+OPS = ('model_forward', 'model_forward_ragged', 'model_backward', 'dtw_loss', 'dtw_align', 'ctc_loss', 'ctc_beam_search', 'ctc_word_beam_search', 'word_ngram_score', 'stft_logmel', 'emg_features', 'fused_adamw',
        'vocoder_conv1d', 'vocoder_conv_transpose1d', 'vocoder_tail')

@@ -1,7 +1,8 @@
 """CTC prefix beam search of a reference-size recognition batch (the batch of tools/ctc_probe.py: 128 000-sample budget, utterances of up to 860
 frames, V = 38) at beam width 100: device time of torch.ops.silent_speech.ctc_beam_search (per-frame lse launch + the one search launch) from
 events -- 3 warm rounds, median and spread of 12 -- and the time per DEPENDENT frame (the frames of the longest utterance run in sequence inside one
-workgroup; the utterances run side by side).  Beside it, on the same batch: beam_decode_utterances with its upload and read-back, greedy_decode_utterances,
+workgroup; the utterances run side by side) -- plain, with a label trigram table fused, and the lexicon-constrained search with a word n-gram
+(ctc_word_beam_search; a seeded random lexicon of 20 000 words with ~4 bigrams and ~4 trigrams per word).  Beside it, on the same batch: beam_decode_utterances with its upload and read-back, greedy_decode_utterances,
 and the ragged forward that produces the logits.  Tuning aid (GPU only)."""
 import statistics
 import time
@@ -46,6 +47,25 @@ def wall_ms(fn):
     return out
 
 
+def random_word_lm(n_words=20000, seed=5):
+    """A lexicon of random lower-case words of 1 .. 8 letters over TextTransform's labels, random natural-log tables."""
+    rng = np.random.default_rng(seed)
+    chars = rm.TextTransform().chars
+    words = set()
+    while len(words) < n_words:
+        words.add(''.join(chars[i] for i in rng.integers(0, 26, rng.integers(1, 9))))
+    words = sorted(words)
+    uni = np.zeros((n_words + 1, 2))
+    x = rng.standard_normal(n_words) * 1.5
+    uni[:n_words, 0] = x - np.log(np.exp(x).sum())
+    uni[:, 1] = -rng.random(n_words + 1)
+    ctx, nxt = rng.integers(0, n_words + 1, 4 * n_words), rng.integers(0, n_words, 4 * n_words)
+    bi = {(int(a), int(b)): (-4 * rng.random(), -rng.random()) for a, b in zip(ctx, nxt)}
+    pairs = sorted(bi)
+    tri = {pairs[j] + (int(w),): -4 * rng.random() for j, w in zip(rng.integers(0, len(pairs), 4 * n_words), rng.integers(0, n_words, 4 * n_words))}
+    return rm.WordNgramLM(words, uni, bi, tri, chars)
+
+
 def line(name, ms, extra=''):
     print('%-58s median %8.3f ms  (min %8.3f, max %8.3f, %d rounds)%s' % (name, statistics.median(ms), min(ms), max(ms), len(ms), extra))
 
@@ -62,6 +82,14 @@ with torch.no_grad():
     table = torch.log_softmax(torch.randn(V, V, V - 1, device=dev), 2).contiguous()
     fused = device_ms(lambda: torch.ops.silent_speech.ctc_beam_search(head, utt, V, V - 1, sum(frames), T, W, 1, table, 0.5, 0.5))
     line('  with a label trigram table fused, device', fused, '  = %.2f us per dependent frame' % (1e3 * statistics.median(fused) / T))
+    wlm = random_word_lm().to(dev)
+    print('word model: %d words, %d lexicon nodes, %d bigrams in %d slots (longest probe %d), %d trigrams in %d slots (longest probe %d)'
+          % (wlm.n_words, wlm.lex_word.numel(), len(wlm.bigrams), wlm.bi_keys.numel(), wlm.bi_probe, len(wlm.trigrams), wlm.tri_keys.numel(), wlm.tri_probe))
+    word = device_ms(lambda: torch.ops.silent_speech.ctc_word_beam_search(head, utt, V, V - 1, V - 2, sum(frames), T, W, 1, wlm.lex_child, wlm.lex_word, wlm.uni, wlm.bi_keys,
+                                                                         wlm.bi_val, wlm.tri_keys, wlm.tri_val, wlm.n_words, wlm.start, wlm.bi_probe, wlm.tri_probe, 0.5, 0.5))
+    line('ctc_word_beam_search op (lexicon + word trigram), device', word, '  = %.2f us per dependent frame' % (1e3 * statistics.median(word) / T))
+    wdec = rm.beam_decode_utterances(logits, beam_width=W, lm=wlm, alpha=0.5, beta=0.5)
+    print('word search: mean decoded length %.1f labels, %.1f words' % (float(np.mean([len(x) for x in wdec])), float(np.mean([1 + x.count(V - 2) for x in wdec]))))
     line('beam_decode_utterances (upload, launches, read-back), wall', wall_ms(lambda: rm.beam_decode_utterances(logits, beam_width=W)))
     line('greedy_decode_utterances (launch, read-back, collapse), wall', wall_ms(lambda: rm.greedy_decode_utterances(logits)))
     line('Model.forward_utterances of the batch, device', device_ms(lambda: model.forward_utterances(raws)))
