@@ -304,7 +304,8 @@ def test_weight_gradient_kernels_at_step_size(cuda):
 
 
 def test_attention_at_step_size(cuda):
-    """B = 110 rows x 8 heads = 880 (sequence, head) pairs: three full rounds of the 256 CUs plus the 112-pair tail that is
-    launched as half-workgroups."""
+    """B = 110 rows x 8 heads = 880 (sequence, head) pairs on the persistent grid of the forward and the query-major backward (256 workgroups on
+    256 CUs, each walking the pairs blockIdx.x, + 256, ...): three full rounds plus a fourth in which 112 workgroups take one more pair and the
+    other 144 have left the loop.  The key-major backward launches one workgroup per pair."""
     from tests.test_attention import _run
     _run(cuda, torch.bfloat16, B=110, H=8, T=200, dh=96, D=100, seed=110, tol_f=2e-2, tol_b=3e-2)
