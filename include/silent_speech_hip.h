@@ -30,9 +30,9 @@ extern "C" {
 const char* ss_last_error(void);
 /* Library/ABI version and the GPU architecture the kernels were compiled for ("gfx950"). */
 /* Bumped whenever a struct layout or an entry-point signature changes (3: ss_gemm_epilogue column-statistics fields, the plan /
- * attention-image / LayerNorm-workspace entry points, ss_dtw_cumulative; 4: ss_loss_index_tables; 5: gate recomputation arguments of ss_bn_backward_sums / ss_bn_backward_apply; 7: ss_split_planes / ss_gemm_planes, ss_dw_job.flags, up to 24 jobs per grouped launch; 8: ss_stft_logmel_fft, the rejected-frame counter behind the matrix of ss_phoneme_confusion; 9: planes_hi / planes_lo / planes_only of ss_gemm_epilogue, dropout groups of the GEMM epilogue are row-major; 10: ss_emg_features_batch; 11: the ss_voc_* vocoder entry points; 12: the ragged-batch inference entry points ss_bn_apply_ragged, ss_relpos_attention_forward_ragged, ss_plan_forward_ragged; 13: ss_ctc_beam_search / ss_ctc_beam_workspace_bytes; 14: ss_word_lm, ss_ctc_word_beam_search / ss_ctc_word_beam_workspace_bytes, ss_word_ngram_score).  Bindings must compare it with SS_ABI_VERSION at load time: a stale
+ * attention-image / LayerNorm-workspace entry points, ss_dtw_cumulative; 4: ss_loss_index_tables; 5: gate recomputation arguments of ss_bn_backward_sums / ss_bn_backward_apply; 7: ss_split_planes / ss_gemm_planes, ss_dw_job.flags, up to 24 jobs per grouped launch; 8: ss_stft_logmel_fft, the rejected-frame counter behind the matrix of ss_phoneme_confusion; 9: planes_hi / planes_lo / planes_only of ss_gemm_epilogue, dropout groups of the GEMM epilogue are row-major; 10: ss_emg_features_batch; 11: the ss_voc_* vocoder entry points; 12: the ragged-batch inference entry points ss_bn_apply_ragged, ss_relpos_attention_forward_ragged, ss_plan_forward_ragged; 13: ss_ctc_beam_search / ss_ctc_beam_workspace_bytes; 14: ss_word_lm, ss_ctc_word_beam_search / ss_ctc_word_beam_workspace_bytes, ss_word_ngram_score; 15: ss_audio_resample_batch / ss_audio_resample_supported / ss_audio_resample_limits, ss_audio_level_batch).  Bindings must compare it with SS_ABI_VERSION at load time: a stale
  * library paired with newer headers would otherwise read garbage struct fields instead of failing. */
-#define SS_ABI_VERSION 14
+#define SS_ABI_VERSION 15
 int ss_abi_version(void);
 const char* ss_target_arch(void);
 
@@ -560,6 +560,34 @@ int ss_linear_resample_batch(const double* x, double* y, const int64_t* table_de
  * column mean, w = the 9-tap box filter applied twice ('same', each pass zero-padding its own input) and p = xs - w; f64 arithmetic, f32
  * store.  table_dev: int64 [R][4] = {first input row, n, first output row, F = n < 16 ? 0 : 1 + (n - 16) / 6}.  1 <= C <= 32. */
 int ss_emg_features_batch(const double* x, float* out, const int64_t* table_dev, int R, int C, int64_t total_frames, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Stored audio (csrc/audio.hip, ABI 15): the resample and the volume levelling of the reference's load_audio (data_utils.py:64-83, :19-27) for a
+ * RAGGED BATCH -- all utterances back to back in one flat f32 buffer -- in one launch each.
+ *
+ * ss_audio_resample_batch is scipy.signal.resample_poly(x, up, down) with its defaults for every utterance: with half = 10 max(up, down) and
+ * h = firwin(2 half + 1, 1 / max(up, down), window = ('kaiser', 5.0)) * up,  y[m] = sum_j x[j] h[m down + half - j up]  over the j inside the utterance
+ * with 0 <= m down + half - j up <= 2 half, n_out = ceil(n up / down) outputs.  The caller designs h (in f64) and hands it over phase-major in f32:
+ * coef_dev [up][taps_per_phase], coef[ph][i] = h[ph + i up] (0 past the end of h), taps_per_phase a multiple of 4 that holds 2 half / up + 1 taps,
+ * 16-byte aligned, device memory.  table_dev: int64 [R][4] = {first input sample, n, first output sample, n_out} per utterance (device memory; n_out
+ * may be smaller than ceil(n up / down): the signal is then cut short; zero-length utterances produce nothing).  An output is the f32 fma chain over
+ * its taps in ascending order: it does not depend on the other utterances of the batch nor on how the batch is tiled.  Epilogue: y *= gains_dev[u]
+ * (NULL = off; what ss_audio_level_batch wrote, or any per-utterance scale), then the clip to [-1, 1] of load_audio when flags bit 0 is set.
+ * flags bit 1 (measurement only): the workgroups read the table through the caches instead of staging it in LDS; same results.
+ * up == down == 1, half = 0 with the table {1, 0, 0, 0} is a copy (with the epilogue).
+ * Supported (ss_audio_resample_supported() == 1; anything else is an error, there is no fallback): up * taps_per_phase <= table_floats,
+ * (tile - 1) * down / up + 1 + taps_per_phase <= span of ss_audio_resample_limits (12288, 2048, 8192) and both together within 64 KB: covers 441/320, 320/441, 147/320, 160/441, 1/2, 2/1. */
+int ss_audio_resample_limits(int* tile, int* span, int* table_floats);
+int ss_audio_resample_supported(int up, int down, int half, int taps_per_phase);
+int ss_audio_resample_batch(const float* x, float* y, const int64_t* table_dev, int R, int up, int down, int half, int taps_per_phase,
+                            const float* coef_dev, const float* gains_dev, int flags, int64_t total_out, void* stream);
+/* What normalize_volume (data_utils.py:19-27) needs, per utterance: level [R][2] = {max over frames of the frame RMS, max |x|}, with the frames of
+ * librosa.feature.rms's defaults (length 2048, hop 512, centred with ZERO padding -- librosa >= 0.10 --, 1 + n / 512 frames), and
+ * gains [R] = 0.2 / (max_rms + 0.01), replaced by 1 / max |x| where that gain would leave the peak above 1.  Either output may be NULL.
+ * table_dev: int64 [R][3] = {first input sample, n, first 512-sample block = sum over the earlier utterances of ceil(n / 512)}; total_blocks = that
+ * sum over all; workspace: 2 * total_blocks floats (the blocks' sums of squares and maxima: every sample is read once).  f32 arithmetic. */
+int ss_audio_level_batch(const float* x, const int64_t* table_dev, int R, int64_t total_blocks, float* workspace, int64_t workspace_floats,
+                         float* level, float* gains, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The execution plan of the transduction model as native code: ONE call enqueues the whole forward pass of Model.forward

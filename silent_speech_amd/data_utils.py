@@ -1,6 +1,8 @@
 """Drop-in for the hot-path parts of the reference's data_utils.py:
 
     mel_spectrogram(y, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, center=False)   (:39-62)
+    normalize_volume(audio) / load_audio(decoded array, sample_rate, ...)                              (:19-27, :64-83; file decoding stays out)
+    resample_audio / resample_audio_batch / volume_gains: the band-limited resample (:75) and the levelling of a ragged batch (csrc/audio.hip)
     get_emg_features(emg_data, debug=False)                                                            (:85-136)
     combine_fixed_length(tensor_list, length) / decollate_tensor(tensor, lengths)                      (:158-178)
     FeatureNormalizer                                                                                   (:138-156)
@@ -255,6 +257,157 @@ def mel_spectrogram_batch(signals, n_fft=1024, num_mels=80, sampling_rate=22050,
                                                 _lib.stream_of(flat)), 'ss_reflect_pad_ragged')
     _stft_logmel(ypad, B, F, ldp, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, out, frame_major=True)
     return out, frames
+
+
+# ------------------------------------------------------------------ stored audio: band-limited resampling and volume levelling (csrc/audio.hip)
+RESAMPLE_TILE, RESAMPLE_SPAN, RESAMPLE_TABLE_FLOATS = 2048, 8192, 12288      # csrc/audio.hip: outputs per tile, bounds of a tile's staged input samples and of the table
+_resample_cache = {}
+
+
+def _rate_ratio(orig_sr, target_sr):
+    for r in (orig_sr, target_sr):
+        if isinstance(r, bool) or int(r) != r or int(r) <= 0:
+            raise ValueError('sample rates must be positive integers (got %r -> %r)' % (orig_sr, target_sr))
+    g = math.gcd(int(orig_sr), int(target_sr))
+    return int(target_sr) // g, int(orig_sr) // g
+
+
+def resample_filter(up, down):
+    """The FIR of scipy.signal.resample_poly(x, up, down) with its defaults, in closed form (f64):
+    firwin(2 half + 1, 1 / max(up, down), window=('kaiser', 5.0)) * up with half = 10 max(up, down).  Returns (h, half); up == down is the copy ([1.], 0)."""
+    if up == down:
+        return np.ones(1), 0
+    mx = max(up, down)
+    half = 10 * mx
+    m = np.arange(2 * half + 1) - float(half)
+    cutoff = 1.0 / mx
+    h = cutoff * np.sinc(cutoff * m)
+    h *= np.i0(5.0 * np.sqrt(1.0 - (m / half) ** 2)) / np.i0(5.0)          # kaiser(beta = 5), symmetric
+    h /= np.sum(h)                                                          # firwin(scale=True): unit gain at 0 Hz
+    return h * up, half
+
+
+def _resample_table(up, down, device):
+    """(coef [up][tpp] f32 on the device, half, tpp): h phase-major -- coef[ph][i] = h[ph + i up], zero past the end, tpp = the taps of the longest
+    phase rounded up to a multiple of 4 --, designed in f64, rounded once, cached per (up, down, device) like the mel basis."""
+    key = (up, down, str(device))
+    if key not in _resample_cache:
+        half = 0 if up == down else 10 * max(up, down)
+        tpp = ((2 * half) // up + 1 + 3) // 4 * 4
+        if not _lib.lib().ss_audio_resample_supported(up, down, half, tpp):
+            raise ValueError('resampling by %d/%d is not supported: its phase table (%d floats) or the input span of a %d-sample output tile exceeds the '
+                             "kernel's bounds (%d floats, %d samples, 64 KB together)" % (up, down, up * tpp, RESAMPLE_TILE, RESAMPLE_TABLE_FLOATS, RESAMPLE_SPAN))
+        h, _ = resample_filter(up, down)
+        pad = np.zeros(up * tpp, dtype=np.float64)
+        pad[:h.shape[0]] = h
+        coef = np.ascontiguousarray(pad.reshape(tpp, up).T).astype(np.float32)
+        _resample_cache[key] = (torch.from_numpy(coef).to(device), half, tpp)
+        _settle_cache(device)
+    return _resample_cache[key]
+
+
+def resampled_length(n, up, down):
+    return (int(n) * up + down - 1) // down
+
+
+def _flat_signals(signals):
+    """list of 1-D tensors / arrays, or (flat, lengths) -> (flat f32 tensor where the kernels read, lengths)."""
+    if isinstance(signals, tuple):
+        flat, lens = signals[0].reshape(-1), [int(n) for n in signals[1]]
+        if flat.dtype != torch.float32 or int(flat.shape[0]) != sum(lens):
+            raise ValueError('packed signals: a flat float32 tensor of sum(lengths) samples')
+    else:
+        ts = [t if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(np.asarray(t))) for t in signals]
+        if any(t.dim() != 1 for t in ts):
+            raise ValueError('every signal must be 1-D')
+        lens = [int(t.shape[0]) for t in ts]
+        flat = torch.cat([t.to(torch.float32) for t in ts]) if len(ts) > 1 else ts[0].to(torch.float32).contiguous()
+    if not lens:
+        raise ValueError('at least one signal is expected')
+    return flat.to(_lib.kernel_device_for(flat)), lens
+
+
+def _resample_rows(flat, out, rows, up, down, gains=None, clip=False):
+    """One ss_audio_resample_batch launch: rows = [(first input sample, n, first output sample, n_out)] into the flat buffers `flat` -> `out`."""
+    from . import staging, torch_ops  # noqa: F401
+    coef, half, tpp = _resample_table(up, down, flat.device)
+    table, = staging.upload([np.asarray(rows, dtype=np.int64).reshape(-1, 4)], flat.device)
+    torch.ops.silent_speech.audio_resample(flat, out, table, coef, gains, up, down, half, tpp, bool(clip), int(sum(r[3] for r in rows)))
+    return out
+
+
+def resample_audio_batch(signals, orig_sr, target_sr, *, gains=None, clip=False):
+    """scipy.signal.resample_poly(x, target_sr / g, orig_sr / g) (the band-limited resample of load_audio, data_utils.py:75; g = gcd) of every signal of
+    a batch in ONE launch.  signals: a list of 1-D signals, or (flat f32 tensor holding them back to back, lengths).  gains: optional per-signal
+    scale (tensor or sequence, e.g. volume_gains) applied to the output; clip: np.clip(., -1, 1) afterwards (:78).  Returns (flat f32 device tensor,
+    lengths) with lengths[u] = ceil(n_u up / down) -- what mel_spectrogram_batch takes."""
+    up, down = _rate_ratio(orig_sr, target_sr)
+    flat, lens = _flat_signals(signals)
+    out_lens = [resampled_length(n, up, down) for n in lens]
+    out = torch.empty(sum(out_lens), dtype=torch.float32, device=flat.device)
+    if gains is not None:
+        gains = torch.as_tensor(gains, dtype=torch.float32).to(flat.device).contiguous()
+        if tuple(gains.shape) != (len(lens),):
+            raise ValueError('one gain per signal')
+    _resample_table(up, down, flat.device)                      # an unsupported ratio is refused even for an empty batch
+    if out.numel():
+        io, oo = np.concatenate([[0], np.cumsum(lens)]), np.concatenate([[0], np.cumsum(out_lens)])
+        _resample_rows(flat, out, [(int(io[u]), lens[u], int(oo[u]), out_lens[u]) for u in range(len(lens))], up, down, gains, clip)
+    return out, out_lens
+
+
+def resample_audio(audio, orig_sr, target_sr, *, clip=False):
+    """One 1-D signal (tensor or array) -> its resample_poly at target_sr, a float32 tensor on the device."""
+    if np.ndim(audio) != 1:
+        raise ValueError('audio must be 1-D')
+    return resample_audio_batch([audio], orig_sr, target_sr, clip=clip)[0]
+
+
+def volume_levels(signals):
+    """(levels [R][2] = {max frame RMS, max |x|}, gains [R]) of normalize_volume for every signal, on the device (librosa.feature.rms defaults of
+    librosa >= 0.10: frames of 2048 every 512 samples, centred with zero padding)."""
+    from . import staging, torch_ops  # noqa: F401
+    flat, lens = _flat_signals(signals)
+    blocks = [(n + 511) // 512 for n in lens]
+    io, bo = np.concatenate([[0], np.cumsum(lens)]), np.concatenate([[0], np.cumsum(blocks)])
+    table, = staging.upload([np.asarray([(int(io[u]), lens[u], int(bo[u])) for u in range(len(lens))], dtype=np.int64)], flat.device)
+    if not flat.numel():
+        flat = flat.new_zeros(1)
+    return torch.ops.silent_speech.audio_level(flat, table, int(bo[-1]))
+
+
+def volume_gains(signals):
+    """normalize_volume's scale per signal (data_utils.py:19-27): 0.2 / (max frame RMS + 0.01), or 1 / max |x| where that would leave the peak above 1.
+    A device f32 tensor [R]; nothing returns to the host."""
+    return volume_levels(signals)[1]
+
+
+def normalize_volume(audio):
+    """data_utils.py:19-27 on the device: a 1-D signal -> the levelled float32 signal."""
+    if np.ndim(audio) != 1:
+        raise ValueError('audio must be 1-D')
+    flat, lens = _flat_signals([audio])
+    return resample_audio_batch((flat, lens), 1, 1, gains=volume_gains((flat, lens)))[0]
+
+
+def load_audio(audio, sample_rate, start=None, end=None, max_frames=None, renormalize_volume=False):
+    """data_utils.py:64-83 from an array already in memory: first channel of a 2-D array, audio[start:end], optional normalize_volume, the band-limited
+    resample to 22 050 Hz when sample_rate differs, clip to [-1, 1], mel_spectrogram(1024, 80, 22050, 256, 1024, 0, 8000) -> (frames, 80) float32 on the
+    device, truncated to max_frames.  Decoding a file is out of scope."""
+    if isinstance(audio, (str, bytes)) or hasattr(audio, '__fspath__'):
+        raise TypeError('load_audio: decoding an audio file is out of scope -- pass the decoded samples and their sample rate')
+    x = audio if torch.is_tensor(audio) else torch.from_numpy(np.ascontiguousarray(np.asarray(audio)))
+    if x.dim() > 1:
+        x = x[:, 0]
+    if start is not None or end is not None:
+        x = x[start:end]
+    flat, lens = _flat_signals([x])
+    gains = volume_gains((flat, lens)) if renormalize_volume else None
+    if int(sample_rate) != 22050 or gains is not None:
+        flat, lens = resample_audio_batch((flat, lens), sample_rate, 22050, gains=gains, clip=True)
+    mel, frames = mel_spectrogram_batch((flat, lens), clip=True)
+    n = frames[0] if max_frames is None else min(frames[0], int(max_frames))
+    return mel[0, :n]
 
 
 def get_emg_features(emg_data, debug=False):

@@ -6,7 +6,8 @@ load_utterance / load_audio do on the CPU per utterance (and lru_cache), done on
     mel_targets(audio, normalizer, ...)     data_utils.py:64-83 + read_emg.py:231   clip -> mel_spectrogram (HIP DFT/mel GEMMs) -> (T, 80) -> normalise
     ShardedSizeAwareSampler                 read_emg.py:115-140   greedy length-budget batches, dealt round-robin to the DP ranks
 
-File decoding and resampling of 16 kHz audio stay on the host (out of scope); the offline EMG filters (read_emg.py:27-71) and the
+File decoding stays on the host (out of scope); audio stored at another rate than 22 050 Hz is resampled on the device
+(data_utils.resample_audio_batch, csrc/audio.hip); the offline EMG filters (read_emg.py:27-71) and the
 hand-crafted EMG features (data_utils.py:85-136) run in DeviceBatchBuilder on the device; everything here starts from arrays already in
 memory.  All functions keep the data on the device and
 enqueue on the current stream; nothing synchronises.
@@ -178,7 +179,8 @@ class DeviceBatchBuilder(object):
     A recording is a dict:
         raw_emg (n, 8)              raw 1 kHz samples of `<idx>_emg.npy`          [+ raw_emg_before / raw_emg_after: the neighbours
                                     load_utterance concatenates as filter context, read_emg.py:55-66]
-        audio (L,)                  waveform at 22 050 Hz, i.e. after load_audio's host-side decode / resample (data_utils.py:65-75)
+        audio (L,)                  decoded waveform (data_utils.py:65-70), at `audio_rate`
+        audio_rate int              optional, default 22 050: the rate `audio` is stored at (the corpus: 16 000); the twin carries its own
         phonemes (frames,) int64    read_phonemes output (optional: 'sil' everywhere like read_emg.py:98)
         silent bool, text_int int64, session_index int
         parallel                    for silent recordings: the voiced twin (same dict shape); its audio features and phonemes become
@@ -187,7 +189,9 @@ class DeviceBatchBuilder(object):
         EMG   : context concat -> 7 notch harmonics + 2 Hz high-pass, zero-phase, f64 (csrc/filters.hip, ragged batch: work items are
                 (chunk, channel) pairs over all recordings) -> crop -> np.interp to 689.06 Hz -> rows 8..8+8n (:90) gathered by one
                 launch -> /20, 50 tanh(./50) (:227-228) in one kernel
-        audio : clip + reflect pad (ragged) -> one hop-strided DFT GEMM -> |.| -> one mel GEMM + log clamp -> FeatureNormalizer, all
+        audio : recordings at another rate than 22 050 Hz: scipy.signal.resample_poly to 22 050 Hz (data_utils.py:75), one launch per distinct rate over
+                the uploaded batch, results in batch order (csrc/audio.hip); every frame count follows the resampled length ceil(L up / down) ->
+                clip + reflect pad (ragged) -> one hop-strided DFT GEMM -> |.| -> one mel GEMM + log clamp -> FeatureNormalizer, all
                 utterances at once (data_utils.mel_spectrogram_batch); truncation to n frames is a view
         features: (emg_features=True) the voiced twins' raw EMG joins the same filter launch sequence, one more resample launch gives
                 the 516.79 Hz signals (:71) of own recordings and twins, their remove_channels columns are zeroed (:73-75), ONE launch
@@ -247,6 +251,22 @@ class DeviceBatchBuilder(object):
             _soft_clip(y, y, y.shape[-1], mean, std, 1.0, 8.0)
         return feats
 
+    @staticmethod
+    def _to_22050(sig, rates):
+        """The batch's audio, packed or a list, with recording u stored at rates[u] -> packed (flat, lengths) at 22 050 Hz in the same order: one
+        resample launch per distinct rate, each reading its recordings from and writing them to their places in the two flat buffers (the
+        recordings already at 22 050 Hz go through the same kernel as a copy)."""
+        from .data_utils import _flat_signals, _rate_ratio, _resample_rows, resampled_length
+        flat, lens = _flat_signals(sig)
+        ratios = [_rate_ratio(r, 22050) for r in rates]
+        out_lens = [resampled_length(n, up, down) for n, (up, down) in zip(lens, ratios)]
+        io, oo = np.concatenate([[0], np.cumsum(lens)]), np.concatenate([[0], np.cumsum(out_lens)])
+        out = torch.empty(int(oo[-1]), dtype=torch.float32, device=flat.device)
+        for ratio in sorted(set(ratios)):
+            rows = [(int(io[u]), lens[u], int(oo[u]), out_lens[u]) for u in range(len(lens)) if ratios[u] == ratio]
+            _resample_rows(flat, out, rows, ratio[0], ratio[1])
+        return out, out_lens
+
     def _frames(self, rec, mel_frames, limit):
         n = min(_feature_frames(len(rec['raw_emg'])), mel_frames)
         return min(n, 800) if limit else n
@@ -289,6 +309,8 @@ class DeviceBatchBuilder(object):
                     side.wait_stream(main)                                                  # device tensors handed in: produced on the caller's stream
                     for t in sig:
                         t.record_stream(side)
+            if any(int(r.get('audio_rate', 22050)) != 22050 for r in audio_src):
+                sig = self._to_22050(sig, [int(r.get('audio_rate', 22050)) for r in audio_src])
             mel, mframes = mel_spectrogram_batch(sig)
             if self.mfcc_norm is not None:
                 mean, std = _normalizer_tensors(self.mfcc_norm, mel.shape[-1], dev)

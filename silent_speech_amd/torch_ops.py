@@ -10,6 +10,7 @@
     word_ngram_score                 ln P(w | w2, w1) of word triples by the device function of that search (tests, n-best rescoring)
     stft_logmel                      data_utils.py:39-62
     emg_features                     data_utils.py:85-136 (get_emg_features; no autograd: the reference's features are numpy)
+    audio_resample / audio_level     the band-limited resample (:75) and normalize_volume's levels (:19-27) of load_audio for a ragged batch of stored audio
     fused_adamw                      torch.optim.AdamW over the flat parameter arena (transduction_model.py:178,210)
     vocoder_conv1d / vocoder_conv_transpose1d / vocoder_tail      the three kernel families of the HiFi-GAN generator (vocoder.py:16-36), inference only
 
@@ -424,6 +425,59 @@ def _(x):
     return x.new_empty((1 + (x.shape[0] - 16) // 6, 14 * x.shape[1]), dtype=torch.float32)
 
 
+# ------------------------------------------------------------------------------------------------ stored audio (csrc/audio.hip; no autograd: data loading)
+@torch.library.custom_op('silent_speech::audio_resample', mutates_args=('out',))
+def audio_resample(flat: Tensor, out: Tensor, table: Tensor, coef: Tensor, gains: Optional[Tensor], up: int, down: int, half: int, taps_per_phase: int,
+                   clip: bool, total_out: int) -> None:
+    """scipy.signal.resample_poly(x, up, down) of every utterance of a ragged batch (ss_audio_resample_batch in include/silent_speech_hip.h).  flat / out:
+    flat f32 buffers; table [R][4] int64 on their device = (first input sample, n, first output sample, n_out) per utterance, all inside the two
+    buffers; coef [up][taps_per_phase] f32: the phase-major filter (data_utils._resample_table); gains: optional [R] f32 scale; clip: to [-1, 1];
+    total_out: the sum of the n_out.  Writes the rows' outputs into `out` and nothing else."""
+    dev = flat.device
+    for t, dt, name in ((flat, torch.float32, 'flat'), (out, torch.float32, 'out'), (table, torch.int64, 'table'), (coef, torch.float32, 'coef')):
+        if t.dtype != dt or not t.is_contiguous() or t.device != dev:
+            raise RuntimeError('audio_resample: %s must be a contiguous %s tensor on the device of the input' % (name, dt))
+    if flat.dim() != 1 or out.dim() != 1 or table.dim() != 2 or table.shape[1] != 4 or table.shape[0] < 1 or tuple(coef.shape) != (up, taps_per_phase):
+        raise RuntimeError('audio_resample: flat buffers, a (R >= 1, 4) table and a (%d, %d) coefficient table are expected' % (up, taps_per_phase))
+    if gains is not None and (gains.dtype != torch.float32 or tuple(gains.shape) != (table.shape[0],) or not gains.is_contiguous() or gains.device != dev):
+        raise RuntimeError('audio_resample: gains must be a contiguous (R) float32 tensor on the device of the input')
+    if not (0 <= total_out <= out.shape[0]):
+        raise RuntimeError('audio_resample: %d outputs do not fit the output buffer of %d' % (total_out, out.shape[0]))
+    if not _L().ss_audio_resample_supported(up, down, half, taps_per_phase):
+        raise ValueError('audio_resample: ratio %d/%d is not supported' % (up, down))
+    if total_out == 0:
+        return
+    _lib.check(_L().ss_audio_resample_batch(_p(flat), _p(out), _p(table), table.shape[0], up, down, half, taps_per_phase, _p(coef), _p(gains),
+                                            1 if clip else 0, total_out, _lib.stream_of(flat)), 'ss_audio_resample_batch')
+
+
+@audio_resample.register_fake
+def _(flat, out, table, coef, gains, up, down, half, taps_per_phase, clip, total_out):
+    return None
+
+
+@torch.library.custom_op('silent_speech::audio_level', mutates_args=())
+def audio_level(flat: Tensor, table: Tensor, total_blocks: int) -> Tuple[Tensor, Tensor]:
+    """normalize_volume's two numbers and its gain per utterance (ss_audio_level_batch): flat f32; table [R][3] int64 = (first sample, n, first 512-sample
+    block).  Returns (levels [R][2] f32 = {max frame RMS, max |x|}, gains [R] f32)."""
+    dev = flat.device
+    if flat.dim() != 1 or flat.dtype != torch.float32 or not flat.is_contiguous():
+        raise RuntimeError('audio_level: a flat contiguous float32 buffer is expected')
+    if table.dim() != 2 or table.shape[1] != 3 or table.shape[0] < 1 or table.dtype != torch.int64 or not table.is_contiguous() or table.device != dev:
+        raise RuntimeError('audio_level: table must be a contiguous (R >= 1, 3) int64 tensor on the device of the input')
+    R = table.shape[0]
+    ws = torch.empty(max(2 * total_blocks, 1), dtype=torch.float32, device=dev)
+    level = torch.empty((R, 2), dtype=torch.float32, device=dev)
+    gains = torch.empty(R, dtype=torch.float32, device=dev)
+    _lib.check(_L().ss_audio_level_batch(_p(flat), _p(table), R, total_blocks, _p(ws), ws.shape[0], _p(level), _p(gains), _lib.stream_of(flat)), 'ss_audio_level_batch')
+    return level, gains
+
+
+@audio_level.register_fake
+def _(flat, table, total_blocks):
+    return flat.new_empty((table.shape[0], 2)), flat.new_empty((table.shape[0],))
+
+
 # ------------------------------------------------------------------------------------------------ fused_adamw
 @torch.library.custom_op('silent_speech::fused_adamw', mutates_args=('p', 'm', 'v'))
 def fused_adamw(p: Tensor, g: Tensor, m: Tensor, v: Tensor, n: int, lr: float, step: int, beta1: float, beta2: float, eps: float,
@@ -493,5 +547,5 @@ def _(x, w, k, slope):
     return x.new_empty((x.shape[0],))
 
 
-OPS = ('model_forward', 'model_forward_ragged', 'model_backward', 'dtw_loss', 'dtw_align', 'ctc_loss', 'ctc_beam_search', 'ctc_word_beam_search', 'word_ngram_score', 'stft_logmel', 'emg_features', 'fused_adamw',
+OPS = ('model_forward', 'model_forward_ragged', 'model_backward', 'dtw_loss', 'dtw_align', 'ctc_loss', 'ctc_beam_search', 'ctc_word_beam_search', 'word_ngram_score', 'stft_logmel', 'emg_features', 'audio_resample', 'audio_level', 'fused_adamw',
        'vocoder_conv1d', 'vocoder_conv_transpose1d', 'vocoder_tail')

@@ -340,27 +340,35 @@ def write_wav(filename, audio, sampling_rate=22050):
         f.writeframes(pcm.tobytes())
 
 
-def save_output(model, datapoint, filename, device, audio_normalizer, vocoder):
+def save_output(model, datapoint, filename, device, audio_normalizer, vocoder, sampling_rate=22050):
     """transduction_model.py:57-73: EMG -> model -> de-normalised mel -> HiFi-GAN -> wav, everything up to the samples on the device
     (vocoder: a silent_speech_amd.vocoder.Vocoder).  Unlike the reference (:73 leaves the model in train mode) the model is returned to
-    the mode it was in."""
+    the mode it was in.  sampling_rate: the rate of the written file; another value than the vocoder's 22 050 Hz resamples its output on the
+    device (data_utils.resample_audio; asr_evaluation.py:20 does this on the host for 16 000 Hz)."""
     y = predict_utterance(model, datapoint, device)
     with torch.no_grad():
         audio = vocoder(_inverse_on_device(audio_normalizer, y))
-    write_wav(filename, audio.cpu().numpy())
+        if int(sampling_rate) != 22050:
+            from .data_utils import resample_audio
+            audio = resample_audio(audio.reshape(-1), 22050, sampling_rate)
+    write_wav(filename, audio.cpu().numpy(), sampling_rate)
 
 
-def save_outputs(model, datapoints, filenames, device, audio_normalizer, vocoder):
+def save_outputs(model, datapoints, filenames, device, audio_normalizer, vocoder, sampling_rate=22050):
     """save_output for a list of utterances: ragged-batch model forward (predict_utterances), the inverse normaliser on the device, ONE batched
-    vocoder call (Vocoder.batch) and a wav per utterance."""
+    vocoder call (Vocoder.batch), ONE resample launch when sampling_rate is not the vocoder's 22 050 Hz, and a wav per utterance."""
     datapoints, filenames = list(datapoints), list(filenames)
     if len(datapoints) != len(filenames):
         raise ValueError('one filename per datapoint')
     ys = predict_utterances(model, datapoints, device)
     with torch.no_grad():
         audios = vocoder.batch([_inverse_on_device(audio_normalizer, y) for y in ys]) if ys else []
+        if audios and int(sampling_rate) != 22050:
+            from .data_utils import resample_audio_batch
+            flat, lens = resample_audio_batch([a.reshape(-1) for a in audios], 22050, sampling_rate)
+            audios = list(torch.split(flat, lens))
     for filename, audio in zip(filenames, audios):
-        write_wav(filename, audio.cpu().numpy())
+        write_wav(filename, audio.cpu().numpy(), sampling_rate)
 
 
 def get_aligned_prediction(model, datapoint, device, audio_normalizer):
