@@ -30,9 +30,9 @@ extern "C" {
 const char* ss_last_error(void);
 /* Library/ABI version and the GPU architecture the kernels were compiled for ("gfx950"). */
 /* Bumped whenever a struct layout or an entry-point signature changes (3: ss_gemm_epilogue column-statistics fields, the plan /
- * attention-image / LayerNorm-workspace entry points, ss_dtw_cumulative; 4: ss_loss_index_tables; 5: gate recomputation arguments of ss_bn_backward_sums / ss_bn_backward_apply; 7: ss_split_planes / ss_gemm_planes, ss_dw_job.flags, up to 24 jobs per grouped launch; 8: ss_stft_logmel_fft, the rejected-frame counter behind the matrix of ss_phoneme_confusion; 9: planes_hi / planes_lo / planes_only of ss_gemm_epilogue, dropout groups of the GEMM epilogue are row-major; 10: ss_emg_features_batch; 11: the ss_voc_* vocoder entry points; 12: the ragged-batch inference entry points ss_bn_apply_ragged, ss_relpos_attention_forward_ragged, ss_plan_forward_ragged; 13: ss_ctc_beam_search / ss_ctc_beam_workspace_bytes; 14: ss_word_lm, ss_ctc_word_beam_search / ss_ctc_word_beam_workspace_bytes, ss_word_ngram_score; 15: ss_audio_resample_batch / ss_audio_resample_supported / ss_audio_resample_limits, ss_audio_level_batch).  Bindings must compare it with SS_ABI_VERSION at load time: a stale
+ * attention-image / LayerNorm-workspace entry points, ss_dtw_cumulative; 4: ss_loss_index_tables; 5: gate recomputation arguments of ss_bn_backward_sums / ss_bn_backward_apply; 7: ss_split_planes / ss_gemm_planes, ss_dw_job.flags, up to 24 jobs per grouped launch; 8: ss_stft_logmel_fft, the rejected-frame counter behind the matrix of ss_phoneme_confusion; 9: planes_hi / planes_lo / planes_only of ss_gemm_epilogue, dropout groups of the GEMM epilogue are row-major; 10: ss_emg_features_batch; 11: the ss_voc_* vocoder entry points; 12: the ragged-batch inference entry points ss_bn_apply_ragged, ss_relpos_attention_forward_ragged, ss_plan_forward_ragged; 13: ss_ctc_beam_search / ss_ctc_beam_workspace_bytes; 14: ss_word_lm, ss_ctc_word_beam_search / ss_ctc_word_beam_workspace_bytes, ss_word_ngram_score; 15: ss_audio_resample_batch / ss_audio_resample_supported / ss_audio_resample_limits, ss_audio_level_batch; 16: ss_spectral_gate_profile / ss_spectral_gate_batch / ss_spectral_gate_limits).  Bindings must compare it with SS_ABI_VERSION at load time: a stale
  * library paired with newer headers would otherwise read garbage struct fields instead of failing. */
-#define SS_ABI_VERSION 15
+#define SS_ABI_VERSION 16
 int ss_abi_version(void);
 const char* ss_target_arch(void);
 
@@ -588,6 +588,29 @@ int ss_audio_resample_batch(const float* x, float* y, const int64_t* table_dev, 
  * sum over all; workspace: 2 * total_blocks floats (the blocks' sums of squares and maxima: every sample is read once).  f32 arithmetic. */
 int ss_audio_level_batch(const float* x, const int64_t* table_dev, int R, int64_t total_blocks, float* workspace, int64_t workspace_floats,
                          float* level, float* gains, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Stationary spectral gating (csrc/spectral_gate.hip, ABI 16): the noise reduction of the reference's data_collection/clean_audio.py:53,
+ * noisereduce 3's stationary gate with its defaults (restated in f64 in tests/spectral_gate_oracle.py), for a RAGGED BATCH in one flat f32 buffer.
+ * N = 1024, hop 256, w = periodic Hann(1024), W = sum w; a signal of L >= 1 samples has F = ceil(L / 256) + 1 frames, frame f covers the samples
+ * [256 f - 512, 256 f + 512) with zeros outside [0, L).  X = (1 / W) rfft(w frame); d = 20 log10(|X| + 2^-52), clamped from below per frequency row at
+ * that row's maximum over the signal's frames - 80; gate = [d > thresh[k]] p + (1 - p); the gate is smoothed by outer(tri(n_f), tri(n_t)) / its sum
+ * with zeros outside the 513 x F mask (tri(n)[d] = (n + 1 - |d|) / (n + 1), |d| <= n); y_f = irfft(X gate) W; out = sum_f w y_f / sum_f w^2 over the
+ * frames that cover a sample, summed in ascending frame order (no floating-point atomics: a batch gives bit for bit what single calls give).
+ * window_dev: 3 x 1024 floats = [w / W | w W / 512 | w^2], designed in f64 and rounded once (data_utils._gate_windows).
+ * table_dev: int64 [R][4] = {first sample, L, first frame = sum of the earlier F, F} per signal (device memory); y uses the same sample offsets as x.
+ * ss_spectral_gate_profile: thresh[k] = mean_f dc[k, .] + n_std std_f dc[k, .] (population std, dc = the clamped d) of ONE noise clip (table of one
+ * row, frames = its F); db_workspace: frames x 513 doubles, rowmax_workspace: 513 dwords.
+ * ss_spectral_gate_batch: thresh [513] f32 in dB (+inf closes a row, -inf opens it); 0 <= n_f <= 32, 0 <= n_t <= 8 (ss_spectral_gate_limits;
+ * anything else is an error, there is no fallback; n_f = n_t = 0 is "no smoothing"); 0 <= prop_decrease <= 1.  Workspaces: bits_workspace
+ * total_frames x 17 dwords (the binary gate, bit k & 31 of dword k >> 5), rowmax_workspace R x 513 dwords, frames_workspace total_frames x 1024 floats
+ * (the windowed frames before the overlap-add).  bits_out (NULL = off): total_frames x 17 dwords, the final gate = own bits | rows opened by the clamp. */
+int ss_spectral_gate_limits(int* max_n_f, int* max_n_t, int* row_dwords);
+int ss_spectral_gate_profile(const float* x, const int64_t* table_dev, int frames, const float* window_dev, double n_std, double* db_workspace,
+                             uint32_t* rowmax_workspace, float* thresh, void* stream);
+int ss_spectral_gate_batch(const float* x, float* y, const int64_t* table_dev, int R, int64_t total_frames, const float* window_dev, const float* thresh,
+                           int n_f, int n_t, double prop_decrease, uint32_t* bits_workspace, uint32_t* rowmax_workspace, float* frames_workspace,
+                           uint32_t* bits_out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The execution plan of the transduction model as native code: ONE call enqueues the whole forward pass of Model.forward

@@ -17,31 +17,17 @@
 // No barrier inside a frame (LDS serves a wave's operations in order; wave_lds_sync is a compiler-level fence), ~26 kFLOP per frame.
 // A wave walks frames g, g + (waves in the grid), ...: its 60 per-lane constants (window, twiddles) are computed once.
 // n_fft is fixed at 1024 (the only value the reference uses); other sizes keep the GEMM formulation (data_utils._stft_logmel).
+// The FFT itself (butterflies, twiddles, tile layout, recombination) lives in fft1024.h, shared with spectral_gate.hip.
 #include "common.h"
+#include "fft1024.h"
 #include "silent_speech_hip.h"
 #include <math.h>
 
 namespace {
-constexpr int MF_N = 1024, MF_H = 512, MF_WAVES = 4;
-constexpr int MF_P1 = 72, MF_P2 = 9;                       // LDS pitches of the two transposes (complex elements)
-constexpr int MF_TILE = 8 * MF_P1;                         // complex elements of a wave's tile
+constexpr int MF_WAVES = 4;
 constexpr int MF_MAXW = 4096, MF_MAXB = 128;               // packed filterbank weights / bands held in LDS
 constexpr int MF_MAGPAD = 8;                               // zeroed magnitudes behind bin 512 (runs are padded to multiples of 4)
 
-typedef float cpx __attribute__((ext_vector_type(2)));     // (re, im)
-__device__ __forceinline__ cpx cmul(cpx a, cpx b) { const cpx bs = {-b[1], b[0]}; return a[0] * b + a[1] * bs; }      // two packed operations
-__device__ __forceinline__ cpx mul_mi(cpx a) { return cpx{a[1], -a[0]}; }                                               // a * (-i)
-// e^(-2 pi i num / den)
-__device__ __forceinline__ cpx twiddle(int num, int den) {
-#if defined(SS_EMU)
-    const double a = -2.0 * 3.14159265358979323846 * (double)num / (double)den;
-    return cpx{(float)cos(a), (float)sin(a)};
-#else
-    float s, c;
-    sincospif(2.0f * (float)num / (float)den, &s, &c);      // the argument is exact (den a power of two)
-    return cpx{c, -s};
-#endif
-}
 __device__ __forceinline__ float fast_sqrt(float x) {
 #if defined(SS_EMU)
     return sqrtf(x);
@@ -49,26 +35,6 @@ __device__ __forceinline__ float fast_sqrt(float x) {
     return __builtin_amdgcn_sqrtf(x);                        // v_sqrt_f32, 1 ulp; the argument is >= 1e-9 (no denormal scaling needed)
 #endif
 }
-// X[k] = sum_q x[q] e^(-2 pi i q k / 8), in place, natural order: one radix-2 split (decimation in frequency) and two 4-point transforms
-__device__ __forceinline__ void dft4(cpx c0, cpx c1, cpx c2, cpx c3, cpx& y0, cpx& y1, cpx& y2, cpx& y3) {
-    const cpx e0 = c0 + c2, e1 = c0 - c2, o0 = c1 + c3, o1 = mul_mi(c1 - c3);
-    y0 = e0 + o0; y2 = e0 - o0; y1 = e1 + o1; y3 = e1 - o1;
-}
-__device__ __forceinline__ void dft8(cpx (&x)[8]) {
-    constexpr float H = 0.70710678118654752f;
-    cpx a[4], b[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) { a[q] = x[q] + x[q + 4]; b[q] = x[q] - x[q + 4]; }
-    b[1] = cpx{b[1][0] + b[1][1], b[1][1] - b[1][0]} * H;            // (1 - i) / sqrt 2
-    b[2] = mul_mi(b[2]);                                               // -i
-    b[3] = cpx{b[3][1] - b[3][0], -(b[3][0] + b[3][1])} * H;         // (-1 - i) / sqrt 2
-    dft4(a[0], a[1], a[2], a[3], x[0], x[2], x[4], x[6]);
-    dft4(b[0], b[1], b[2], b[3], x[1], x[3], x[5], x[7]);
-}
-// position of Z[k] in the tile: a skew of 4 elements per 32, so that the pass-3 stores (k = k0 + 8 k0' + 64 k1' over the lanes (k0, k0')) and the
-// recombination's reads (k = lane + 64 j, and 512 - k) both touch 32 distinct 8-byte bank pairs per half wave
-__device__ __forceinline__ int zpos(int k) { return k + 4 * (k >> 5); }
-static_assert(MF_H - 1 + 4 * ((MF_H - 1) >> 5) < MF_TILE, "the skewed spectrum fits the tile");
 }
 
 // (3 workgroups per CU: 168 registers; left alone hipcc takes 224 -- two waves per SIMD -- and the kernel runs 15-30 % slower: tools/mel_probe.py)
@@ -88,13 +54,12 @@ __global__ __launch_bounds__(MF_WAVES * 64, 3) void stft_logmel_fft_kernel(const
     __syncthreads();
 
     // ---- per-lane constants
-    const int r = lane, k0l = lane >> 3, r0 = lane & 7;            // pass 1: lane = r; pass 2: lane = (k0, r0); pass 3: lane = (k0, k0')
+    const int r = lane;                                            // pass 1 of the FFT (fft1024.h): lane r holds z[r + 64 q]
     cpx win[8];
 #pragma unroll
     for (int q = 0; q < 8; ++q) { const int n = r + 64 * q; win[q] = cpx{window[2 * n], window[2 * n + 1]}; }
     cpx tw1[8], tw2[8], tw3[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { tw1[k] = twiddle(r * k, MF_H); tw2[k] = twiddle(r0 * k, 64); tw3[k] = twiddle(lane + 64 * k, MF_N); }
+    fft512_twiddles(lane, tw1, tw2, tw3);
     const cpx tw_nyq = twiddle(MF_H, MF_N);
     int bm[2], blo[2], bcnt[2], boff[2];                           // this lane's (at most two) bands
 #pragma unroll
@@ -135,39 +100,16 @@ __global__ __launch_bounds__(MF_WAVES * 64, 3) void stft_logmel_fft_kernel(const
         }
 #pragma unroll
         for (int q = 0; q < 8; ++q) v[q] *= win[q];
-        dft8(v);
-        wave_lds_sync();                                           // (the previous frame's reads of the tile are behind us)
-#pragma unroll
-        for (int k = 0; k < 8; ++k) tl[k * MF_P1 + r] = k ? cmul(v[k], tw1[k]) : v[k];
-        wave_lds_sync();
-        // ---- pass 2: lane (k0, r0): T[k0][r0 + 8 r1], r1 = 0 .. 7 -> radix 8 over r1 -> U[k0][r0][k0'] = W_64^(r0 k0') sum_r1 T W_8^(r1 k0')
-#pragma unroll
-        for (int r1 = 0; r1 < 8; ++r1) v[r1] = tl[k0l * MF_P1 + r0 + 8 * r1];
-        dft8(v);
-        wave_lds_sync();
-#pragma unroll
-        for (int k = 0; k < 8; ++k) tl[k0l * MF_P1 + r0 * MF_P2 + k] = k ? cmul(v[k], tw2[k]) : v[k];
-        wave_lds_sync();
-        // ---- pass 3: lane (k0, k0' = lane & 7): U[k0][r0][k0'], r0 = 0 .. 7 -> radix 8 over r0 -> Z[k0 + 8 k0' + 64 k1']
-#pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] = tl[k0l * MF_P1 + q * MF_P2 + r0];
-        dft8(v);
-        wave_lds_sync();
-#pragma unroll
-        for (int k = 0; k < 8; ++k) tl[zpos(k0l + 8 * r0 + 64 * k)] = v[k];
-        wave_lds_sync();
+        fft512(v, tl, lane, tw1, tw2);                             // three radix-8 passes: Z[k] at tl[zpos(k)]
         // ---- the real signal's bins k = lane + 64 j (and k = 512): X[k] = E + W_1024^k O, E = (Z[k] + conj Z[512 - k]) / 2, O = (Z[k] - conj Z[512 - k]) / (2 i)
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const int k = lane + 64 * j, km = (MF_H - k) & (MF_H - 1);
-            const cpx a = tl[zpos(k)], c0 = tl[zpos(km)], c = cpx{c0[0], -c0[1]};
-            const cpx e = 0.5f * (a + c), o = mul_mi(0.5f * (a - c));
-            const cpx xk = e + cmul(o, tw3[j]);
+            const int k = lane + 64 * j;
+            const cpx xk = rfft_bin(tl, k, tw3[j]);
             mg[k] = fast_sqrt(xk[0] * xk[0] + xk[1] * xk[1] + 1e-9f);
         }
         if (lane == 0) {                                           // k = 512: Z[512] = Z[0]: E = re Z[0], O = im Z[0]
-            const cpx a = tl[0];
-            const cpx xk = cpx{a[0], 0.f} + cmul(cpx{a[1], 0.f}, tw_nyq);
+            const cpx xk = rfft_nyquist(tl, tw_nyq);
             mg[MF_H] = fast_sqrt(xk[0] * xk[0] + xk[1] * xk[1] + 1e-9f);
         }
         wave_lds_sync();

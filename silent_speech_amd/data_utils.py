@@ -3,6 +3,8 @@
     mel_spectrogram(y, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, center=False)   (:39-62)
     normalize_volume(audio) / load_audio(decoded array, sample_rate, ...)                              (:19-27, :64-83; file decoding stays out)
     resample_audio / resample_audio_batch / volume_gains: the band-limited resample (:75) and the levelling of a ragged batch (csrc/audio.hip)
+    NoiseProfile / reduce_noise / reduce_noise_batch / clean_session: the stationary spectral gate and the levelling of data_collection/clean_audio.py
+                                                                     (noisereduce's reduce_noise, csrc/spectral_gate.hip; file decoding stays out)
     get_emg_features(emg_data, debug=False)                                                            (:85-136)
     combine_fixed_length(tensor_list, length) / decollate_tensor(tensor, lengths)                      (:158-178)
     FeatureNormalizer                                                                                   (:138-156)
@@ -408,6 +410,153 @@ def load_audio(audio, sample_rate, start=None, end=None, max_frames=None, renorm
     mel, frames = mel_spectrogram_batch((flat, lens), clip=True)
     n = frames[0] if max_frames is None else min(frames[0], int(max_frames))
     return mel[0, :n]
+
+
+# ------------------------------------------------------------------ noise reduction: stationary spectral gating (csrc/spectral_gate.hip)
+GATE_N_FFT, GATE_HOP, GATE_BINS, GATE_MAX_NF, GATE_MAX_NT = 1024, 256, 513, 32, 8       # the sizes noisereduce uses; bounds of the mask smoothing
+_gate_cache = {}
+
+
+def _gate_windows(device):
+    """(3, 1024) f32 on the device: [w / W | w W / 512 | w^2] of the periodic Hann window w, W = sum w; designed in f64, rounded once, cached."""
+    key = str(device)
+    if key not in _gate_cache:
+        w = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(GATE_N_FFT) / GATE_N_FFT)
+        W = float(w.sum())
+        _gate_cache[key] = torch.from_numpy(np.stack([w / W, w * (W / 512.0), w * w]).astype(np.float32)).to(device)
+        _settle_cache(device)
+    return _gate_cache[key]
+
+
+def gate_frames(n):
+    """frames of a signal of n >= 1 samples: ceil(n / 256) + 1 (centred frames of 1024 every 256 samples, the last one at or behind the end)."""
+    return (int(n) + GATE_HOP - 1) // GATE_HOP + 1
+
+
+def gate_smoothing(sample_rate, freq_mask_smooth_hz=500, time_mask_smooth_ms=50):
+    """(n_f, n_t): half widths of the mask's triangular smoothing as noisereduce derives them (513 rows over sr / 2, frames of 256 samples); both
+    arguments None: no smoothing.  Refused beyond the kernel's 32 rows x 8 frames."""
+    if not (float(sample_rate) > 0):
+        raise ValueError('the sample rate must be positive (got %r)' % (sample_rate,))
+    if freq_mask_smooth_hz is None and time_mask_smooth_ms is None:
+        return 0, 0
+    n_f = 0 if freq_mask_smooth_hz is None else int(freq_mask_smooth_hz / (sample_rate / 512))
+    n_t = 0 if time_mask_smooth_ms is None else int(time_mask_smooth_ms / (256000 / sample_rate))
+    if not (0 <= n_f <= GATE_MAX_NF and 0 <= n_t <= GATE_MAX_NT):
+        raise ValueError('mask smoothing over %d frequency rows x %d frames (%r Hz, %r ms at %r Hz) is not supported: at most %d x %d'
+                         % (n_f, n_t, freq_mask_smooth_hz, time_mask_smooth_ms, sample_rate, GATE_MAX_NF, GATE_MAX_NT))
+    return n_f, n_t
+
+
+def _gate_table(lens, device, rows=None):
+    """(table (R, 4) int64 on the device = (first sample, L, first frame, F) of the signals `rows` (default: all) of a flat buffer that holds signals of
+    `lens` samples back to back, total frames)"""
+    from . import staging
+    rows = list(range(len(lens))) if rows is None else list(rows)
+    if any(lens[u] < 1 for u in rows):
+        raise ValueError('an empty signal cannot be gated')
+    if any(lens[u] >= 2 ** 31 - 2048 for u in rows):
+        raise ValueError('signals of 2^31 samples and more are not supported')
+    io = np.concatenate([[0], np.cumsum(lens)])
+    frames = [gate_frames(lens[u]) for u in rows]
+    fo = np.concatenate([[0], np.cumsum(frames)])
+    table, = staging.upload([np.stack([[int(io[u]) for u in rows], [lens[u] for u in rows], fo[:-1], frames], 1).astype(np.int64)], device)
+    return table, int(fo[-1])
+
+
+def _gate_rows(flat, out, lens, rows, profile, n_f, n_t, prop_decrease=1.0, return_bits=False):
+    """One ss_spectral_gate_batch launch sequence: the signals `rows` of the flat buffer `flat` -> their places in `out`."""
+    from . import torch_ops  # noqa: F401
+    table, total_frames = _gate_table(lens, flat.device, rows)
+    return torch.ops.silent_speech.spectral_gate(flat, out, table, _gate_windows(flat.device), profile.thresh.to(flat.device), total_frames, n_f, n_t,
+                                                 float(prop_decrease), bool(return_bits))
+
+
+class NoiseProfile(object):
+    """The stationary gate's threshold per frequency row: thresh (513,) f32 in dB on the device, with the sample rate and n_std it was made for."""
+
+    def __init__(self, thresh, sample_rate, n_std_thresh_stationary=1.5):
+        if tuple(thresh.shape) != (GATE_BINS,) or thresh.dtype != torch.float32:
+            raise ValueError('thresh: a (513,) float32 tensor')
+        self.thresh, self.sr, self.n_std = thresh.contiguous(), sample_rate, float(n_std_thresh_stationary)
+
+    @classmethod
+    def from_noise(cls, noise, sample_rate, n_std_thresh_stationary=1.5):
+        """mean + n_std * std (population) over the noise clip's frames of 20 log10(|STFT| + eps), clamped per row at its maximum - 80."""
+        from . import torch_ops  # noqa: F401
+        if not (float(sample_rate) > 0):
+            raise ValueError('the sample rate must be positive (got %r)' % (sample_rate,))
+        if np.ndim(noise) != 1 or len(noise) == 0:
+            raise ValueError('the noise clip must be 1-D and non-empty')
+        flat, lens = _flat_signals([noise])
+        table, frames = _gate_table(lens, flat.device)
+        thresh = torch.ops.silent_speech.spectral_gate_profile(flat, table, _gate_windows(flat.device), frames, float(n_std_thresh_stationary))
+        return cls(thresh, sample_rate, n_std_thresh_stationary)
+
+
+def reduce_noise_batch(signals, profile, *, prop_decrease=1.0, freq_mask_smooth_hz=500, time_mask_smooth_ms=50, return_bits=False):
+    """noisereduce.reduce_noise(y, sr, y_noise, stationary=True) of every signal of a batch against ONE NoiseProfile, one launch per kernel for the whole
+    batch.  signals: a list of 1-D signals, or (flat f32 tensor, lengths) as for resample_audio_batch.  Returns (flat f32 device tensor, lengths) --
+    and the final binary gate (total frames, 17) int32 as a third item with return_bits."""
+    if not isinstance(profile, NoiseProfile):
+        raise TypeError('profile: a NoiseProfile (NoiseProfile.from_noise(noise, sample_rate))')
+    if not (0.0 <= float(prop_decrease) <= 1.0):
+        raise ValueError('prop_decrease must lie in [0, 1]')
+    n_f, n_t = gate_smoothing(profile.sr, freq_mask_smooth_hz, time_mask_smooth_ms)
+    flat, lens = _flat_signals(signals)
+    out = torch.empty_like(flat)
+    bits = _gate_rows(flat, out, lens, None, profile, n_f, n_t, prop_decrease, return_bits)
+    return (out, lens, bits) if return_bits else (out, lens)
+
+
+def reduce_noise(y, sr, y_noise=None, *, profile=None, stationary=True, prop_decrease=1.0, n_std_thresh_stationary=1.5, freq_mask_smooth_hz=500,
+                 time_mask_smooth_ms=50):
+    """noisereduce.reduce_noise(y=y, sr=sr, y_noise=y_noise, stationary=True, ...) (data_collection/clean_audio.py:53) on the device: a float32 tensor of
+    len(y) samples.  The threshold comes from `profile`, else from y_noise, else from y itself."""
+    if not stationary:
+        raise NotImplementedError('reduce_noise: the non-stationary gate is out of scope; only stationary=True is built')
+    if not (float(sr) > 0):
+        raise ValueError('the sample rate must be positive (got %r)' % (sr,))
+    if np.ndim(y) != 1 or len(y) == 0:
+        raise ValueError('y must be 1-D and non-empty')
+    if profile is None:
+        if y_noise is not None and (np.ndim(y_noise) != 1 or len(y_noise) == 0):
+            raise ValueError('the noise clip must be 1-D and non-empty')
+        profile = NoiseProfile.from_noise(y if y_noise is None else y_noise, sr, n_std_thresh_stationary)
+    return reduce_noise_batch([y], profile, prop_decrease=prop_decrease, freq_mask_smooth_hz=freq_mask_smooth_hz, time_mask_smooth_ms=time_mask_smooth_ms)[0]
+
+
+def session_gains(max_rmses, silent_cutoff=0.02, smoothing_width=20, target_rms=0.2):
+    """clean_audio.py:33-47 on the host (a few dozen scalars): file i's gain is target_rms / the mean of the max frame RMS values above the cutoff among
+    the files i - 20 .. i + 20; None when some file has no such neighbour ("long run of quiet audio": no levelling at all)."""
+    m = [float(v) for v in max_rmses]
+    gains = []
+    for i in range(len(m)):
+        vs = [m[j] for j in range(max(0, i - smoothing_width), min(i + 1 + smoothing_width, len(m))) if m[j] > silent_cutoff]
+        if not vs:
+            return None
+        gains.append(target_rms / float(np.mean(vs)))
+    return gains
+
+
+def clean_session(signals, sample_rate, noise=None):
+    """data_collection/clean_audio.py clean_directory from decoded arrays: the session's recordings in file order (signals[0] is the silence clip
+    0_audio unless `noise` is given) -> (flat f32 device tensor at 22 050 Hz, lengths).  Max frame RMS per file (volume_levels on the raw signals) ->
+    the +-20-file smoothing on the host -> the stationary gate against the noise clip's profile -> the band-limited resample to 22 050 Hz with the
+    gain 0.2 / smoothed max -> x / max |x| * 0.99 where the peak exceeds 0.99.  A long run of quiet audio skips the levelling, as the reference does."""
+    flat, lens = _flat_signals(signals)
+    levels = volume_levels((flat, lens))[0][:, 0].cpu().tolist()
+    gains = session_gains(levels)
+    if noise is None:
+        noise = flat[:lens[0]]
+    profile = NoiseProfile.from_noise(noise, sample_rate)
+    clean, lens = reduce_noise_batch((flat, lens), profile)
+    out, out_lens = resample_audio_batch((clean, lens), sample_rate, 22050, gains=gains)
+    if gains is not None:
+        peak = volume_levels((out, out_lens))[0][:, 1]
+        scale = torch.where(peak > 0.99, 0.99 / peak, torch.ones_like(peak))
+        out, out_lens = resample_audio_batch((out, out_lens), 1, 1, gains=scale)
+    return out, out_lens
 
 
 def get_emg_features(emg_data, debug=False):

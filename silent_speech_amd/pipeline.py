@@ -181,6 +181,8 @@ class DeviceBatchBuilder(object):
                                     load_utterance concatenates as filter context, read_emg.py:55-66]
         audio (L,)                  decoded waveform (data_utils.py:65-70), at `audio_rate`
         audio_rate int              optional, default 22 050: the rate `audio` is stored at (the corpus: 16 000); the twin carries its own
+        noise_profile               optional data_utils.NoiseProfile (of the session's silence clip, at the stored rate): the audio goes through the
+                                    stationary spectral gate (data_collection/clean_audio.py:53) before anything else; the twin carries its own
         phonemes (frames,) int64    read_phonemes output (optional: 'sil' everywhere like read_emg.py:98)
         silent bool, text_int int64, session_index int
         parallel                    for silent recordings: the voiced twin (same dict shape); its audio features and phonemes become
@@ -189,7 +191,9 @@ class DeviceBatchBuilder(object):
         EMG   : context concat -> 7 notch harmonics + 2 Hz high-pass, zero-phase, f64 (csrc/filters.hip, ragged batch: work items are
                 (chunk, channel) pairs over all recordings) -> crop -> np.interp to 689.06 Hz -> rows 8..8+8n (:90) gathered by one
                 launch -> /20, 50 tanh(./50) (:227-228) in one kernel
-        audio : recordings at another rate than 22 050 Hz: scipy.signal.resample_poly to 22 050 Hz (data_utils.py:75), one launch per distinct rate over
+        audio : recordings with a noise_profile: noisereduce's stationary gate at the stored rate, one launch sequence per distinct profile over the
+                uploaded batch (csrc/spectral_gate.hip); recordings without one are passed on as they are ->
+                recordings at another rate than 22 050 Hz: scipy.signal.resample_poly to 22 050 Hz (data_utils.py:75), one launch per distinct rate over
                 the uploaded batch, results in batch order (csrc/audio.hip); every frame count follows the resampled length ceil(L up / down) ->
                 clip + reflect pad (ragged) -> one hop-strided DFT GEMM -> |.| -> one mel GEMM + log clamp -> FeatureNormalizer, all
                 utterances at once (data_utils.mel_spectrogram_batch); truncation to n frames is a view
@@ -267,6 +271,23 @@ class DeviceBatchBuilder(object):
             _resample_rows(flat, out, rows, ratio[0], ratio[1])
         return out, out_lens
 
+    @staticmethod
+    def _gated(sig, recs):
+        """The batch's audio with the recordings that carry a noise_profile replaced by their gated signals (reduce_noise with its defaults at the
+        recording's stored rate), in the same order and layout: one launch sequence per distinct profile."""
+        from .data_utils import _flat_signals, _gate_rows, gate_smoothing
+        flat, lens = _flat_signals(sig)
+        profiles = [r.get('noise_profile') for r in recs]
+        out = torch.empty_like(flat) if all(p is not None for p in profiles) else flat.clone()
+        done = set()
+        for p in profiles:
+            if p is None or id(p) in done:
+                continue
+            done.add(id(p))
+            n_f, n_t = gate_smoothing(p.sr)
+            _gate_rows(flat, out, lens, [u for u, q in enumerate(profiles) if q is p], p, n_f, n_t)
+        return out, lens
+
     def _frames(self, rec, mel_frames, limit):
         n = min(_feature_frames(len(rec['raw_emg'])), mel_frames)
         return min(n, 800) if limit else n
@@ -309,6 +330,8 @@ class DeviceBatchBuilder(object):
                     side.wait_stream(main)                                                  # device tensors handed in: produced on the caller's stream
                     for t in sig:
                         t.record_stream(side)
+            if any(r.get('noise_profile') is not None for r in audio_src):
+                sig = self._gated(sig, audio_src)
             if any(int(r.get('audio_rate', 22050)) != 22050 for r in audio_src):
                 sig = self._to_22050(sig, [int(r.get('audio_rate', 22050)) for r in audio_src])
             mel, mframes = mel_spectrogram_batch(sig)

@@ -11,6 +11,7 @@
     stft_logmel                      data_utils.py:39-62
     emg_features                     data_utils.py:85-136 (get_emg_features; no autograd: the reference's features are numpy)
     audio_resample / audio_level     the band-limited resample (:75) and normalize_volume's levels (:19-27) of load_audio for a ragged batch of stored audio
+    spectral_gate_profile / spectral_gate      the stationary noise gate of data_collection/clean_audio.py:53 (noisereduce's reduce_noise) for a ragged batch
     fused_adamw                      torch.optim.AdamW over the flat parameter arena (transduction_model.py:178,210)
     vocoder_conv1d / vocoder_conv_transpose1d / vocoder_tail      the three kernel families of the HiFi-GAN generator (vocoder.py:16-36), inference only
 
@@ -478,6 +479,76 @@ def _(flat, table, total_blocks):
     return flat.new_empty((table.shape[0], 2)), flat.new_empty((table.shape[0],))
 
 
+# ------------------------------------------------------------------------------------------------ spectral gating (csrc/spectral_gate.hip; no autograd: data preparation)
+GATE_BINS, GATE_ROW_DWORDS, GATE_MAX_NF, GATE_MAX_NT = 513, 17, 32, 8
+
+
+def _gate_check(name, flat, table, windows):
+    dev = flat.device
+    if flat.dim() != 1 or flat.dtype != torch.float32 or not flat.is_contiguous():
+        raise RuntimeError('%s: a flat contiguous float32 buffer is expected' % name)
+    if table.dim() != 2 or table.shape[1] != 4 or table.shape[0] < 1 or table.dtype != torch.int64 or not table.is_contiguous() or table.device != dev:
+        raise RuntimeError('%s: table must be a contiguous (R >= 1, 4) int64 tensor on the device of the input' % name)
+    if tuple(windows.shape) != (3, 1024) or windows.dtype != torch.float32 or not windows.is_contiguous() or windows.device != dev:
+        raise RuntimeError('%s: windows must be a contiguous (3, 1024) float32 tensor on the device of the input' % name)
+
+
+@torch.library.custom_op('silent_speech::spectral_gate_profile', mutates_args=())
+def spectral_gate_profile(flat: Tensor, table: Tensor, windows: Tensor, frames: int, n_std: float) -> Tensor:
+    """The stationary gate's threshold per frequency row from ONE noise clip (ss_spectral_gate_profile): flat f32 holding the clip; table (1, 4) int64 =
+    (first sample, L, 0, F = ceil(L / 256) + 1); windows (3, 1024) f32 (data_utils._gate_windows); frames = F.  Returns thresh (513,) f32 in dB:
+    mean + n_std * population std over the frames of 20 log10(|X| + eps) clamped at the row's maximum - 80."""
+    _gate_check('spectral_gate_profile', flat, table, windows)
+    if table.shape[0] != 1 or frames < 2:
+        raise ValueError('spectral_gate_profile: one non-empty noise clip is expected')
+    dev = flat.device
+    db = torch.empty((frames, GATE_BINS), dtype=torch.float64, device=dev)
+    rowmax = torch.empty(GATE_BINS, dtype=torch.int32, device=dev)
+    thresh = torch.empty(GATE_BINS, dtype=torch.float32, device=dev)
+    _lib.check(_L().ss_spectral_gate_profile(_p(flat), _p(table), frames, _p(windows), float(n_std), _p(db), _p(rowmax), _p(thresh), _lib.stream_of(flat)),
+               'ss_spectral_gate_profile')
+    return thresh
+
+
+@spectral_gate_profile.register_fake
+def _(flat, table, windows, frames, n_std):
+    return flat.new_empty((GATE_BINS,))
+
+
+@torch.library.custom_op('silent_speech::spectral_gate', mutates_args=('out',))
+def spectral_gate(flat: Tensor, out: Tensor, table: Tensor, windows: Tensor, thresh: Tensor, total_frames: int, n_f: int, n_t: int, prop_decrease: float,
+                  return_bits: bool) -> Tensor:
+    """noisereduce's stationary gate over every signal of a ragged batch (ss_spectral_gate_batch in include/silent_speech_hip.h).  flat: f32 buffer; table
+    (R, 4) int64 = (first sample, L, first frame, F) per signal; thresh (513,) f32 in dB; n_f / n_t: half widths of the mask's triangular smoothing over
+    frequency rows / frames (0, 0 = none).  Writes the gated signals into `out` (flat's layout and size; nothing else of it is touched) and returns the
+    final binary gate (total_frames, 17) int32 -- bit k & 31 of dword k >> 5 -- when return_bits, else an empty (0, 17) tensor."""
+    _gate_check('spectral_gate', flat, table, windows)
+    dev = flat.device
+    if tuple(thresh.shape) != (GATE_BINS,) or thresh.dtype != torch.float32 or not thresh.is_contiguous() or thresh.device != dev:
+        raise RuntimeError('spectral_gate: thresh must be a contiguous (513,) float32 tensor on the device of the input')
+    if not (0 <= n_f <= GATE_MAX_NF and 0 <= n_t <= GATE_MAX_NT):
+        raise ValueError('spectral_gate: mask smoothing over %d rows x %d frames is not supported (at most %d x %d)' % (n_f, n_t, GATE_MAX_NF, GATE_MAX_NT))
+    if not (0.0 <= prop_decrease <= 1.0):
+        raise ValueError('spectral_gate: prop_decrease must lie in [0, 1]')
+    R = table.shape[0]
+    if total_frames < 2 * R:
+        raise ValueError('spectral_gate: every signal needs at least one sample')
+    if out.shape != flat.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise RuntimeError('spectral_gate: out must be a contiguous float32 buffer of the size and on the device of the input')
+    bits_ws = torch.empty((total_frames, GATE_ROW_DWORDS), dtype=torch.int32, device=dev)
+    rowmax = torch.empty((R, GATE_BINS), dtype=torch.int32, device=dev)
+    frames = torch.empty((total_frames, 1024), dtype=torch.float32, device=dev)
+    bits = torch.empty((total_frames if return_bits else 0, GATE_ROW_DWORDS), dtype=torch.int32, device=dev)
+    _lib.check(_L().ss_spectral_gate_batch(_p(flat), _p(out), _p(table), R, total_frames, _p(windows), _p(thresh), n_f, n_t, float(prop_decrease), _p(bits_ws),
+                                           _p(rowmax), _p(frames), _p(bits) if return_bits else None, _lib.stream_of(flat)), 'ss_spectral_gate_batch')
+    return bits
+
+
+@spectral_gate.register_fake
+def _(flat, out, table, windows, thresh, total_frames, n_f, n_t, prop_decrease, return_bits):
+    return flat.new_empty((total_frames if return_bits else 0, GATE_ROW_DWORDS), dtype=torch.int32)
+
+
 # ------------------------------------------------------------------------------------------------ fused_adamw
 @torch.library.custom_op('silent_speech::fused_adamw', mutates_args=('p', 'm', 'v'))
 def fused_adamw(p: Tensor, g: Tensor, m: Tensor, v: Tensor, n: int, lr: float, step: int, beta1: float, beta2: float, eps: float,
@@ -547,5 +618,5 @@ def _(x, w, k, slope):
     return x.new_empty((x.shape[0],))
 
 
-OPS = ('model_forward', 'model_forward_ragged', 'model_backward', 'dtw_loss', 'dtw_align', 'ctc_loss', 'ctc_beam_search', 'ctc_word_beam_search', 'word_ngram_score', 'stft_logmel', 'emg_features', 'audio_resample', 'audio_level', 'fused_adamw',
+OPS = ('model_forward', 'model_forward_ragged', 'model_backward', 'dtw_loss', 'dtw_align', 'ctc_loss', 'ctc_beam_search', 'ctc_word_beam_search', 'word_ngram_score', 'stft_logmel', 'emg_features', 'audio_resample', 'audio_level', 'spectral_gate_profile', 'spectral_gate', 'fused_adamw',
        'vocoder_conv1d', 'vocoder_conv_transpose1d', 'vocoder_tail')
