@@ -30,9 +30,9 @@ extern "C" {
 const char* ss_last_error(void);
 /* Library/ABI version and the GPU architecture the kernels were compiled for ("gfx950"). */
 /* Bumped whenever a struct layout or an entry-point signature changes (3: ss_gemm_epilogue column-statistics fields, the plan /
- * attention-image / LayerNorm-workspace entry points, ss_dtw_cumulative; 4: ss_loss_index_tables; 5: gate recomputation arguments of ss_bn_backward_sums / ss_bn_backward_apply; 7: ss_split_planes / ss_gemm_planes, ss_dw_job.flags, up to 24 jobs per grouped launch; 8: ss_stft_logmel_fft, the rejected-frame counter behind the matrix of ss_phoneme_confusion; 9: planes_hi / planes_lo / planes_only of ss_gemm_epilogue, dropout groups of the GEMM epilogue are row-major; 10: ss_emg_features_batch; 11: the ss_voc_* vocoder entry points; 12: the ragged-batch inference entry points ss_bn_apply_ragged, ss_relpos_attention_forward_ragged, ss_plan_forward_ragged; 13: ss_ctc_beam_search / ss_ctc_beam_workspace_bytes; 14: ss_word_lm, ss_ctc_word_beam_search / ss_ctc_word_beam_workspace_bytes, ss_word_ngram_score; 15: ss_audio_resample_batch / ss_audio_resample_supported / ss_audio_resample_limits, ss_audio_level_batch; 16: ss_spectral_gate_profile / ss_spectral_gate_batch / ss_spectral_gate_limits).  Bindings must compare it with SS_ABI_VERSION at load time: a stale
+ * attention-image / LayerNorm-workspace entry points, ss_dtw_cumulative; 4: ss_loss_index_tables; 5: gate recomputation arguments of ss_bn_backward_sums / ss_bn_backward_apply; 7: ss_split_planes / ss_gemm_planes, ss_dw_job.flags, up to 24 jobs per grouped launch; 8: ss_stft_logmel_fft, the rejected-frame counter behind the matrix of ss_phoneme_confusion; 9: planes_hi / planes_lo / planes_only of ss_gemm_epilogue, dropout groups of the GEMM epilogue are row-major; 10: ss_emg_features_batch; 11: the ss_voc_* vocoder entry points; 12: the ragged-batch inference entry points ss_bn_apply_ragged, ss_relpos_attention_forward_ragged, ss_plan_forward_ragged; 13: ss_ctc_beam_search / ss_ctc_beam_workspace_bytes; 14: ss_word_lm, ss_ctc_word_beam_search / ss_ctc_word_beam_workspace_bytes, ss_word_ngram_score; 15: ss_audio_resample_batch / ss_audio_resample_supported / ss_audio_resample_limits, ss_audio_level_batch; 16: ss_spectral_gate_profile / ss_spectral_gate_batch / ss_spectral_gate_limits; 17: ss_stft_logmel_fft_backward / ss_stft_logmel_fft_backward_workspace_bytes).  Bindings must compare it with SS_ABI_VERSION at load time: a stale
  * library paired with newer headers would otherwise read garbage struct fields instead of failing. */
-#define SS_ABI_VERSION 16
+#define SS_ABI_VERSION 17
 int ss_abi_version(void);
 const char* ss_target_arch(void);
 
@@ -463,6 +463,20 @@ int ss_stft_logmel_fft(const float* y, const int64_t* offsets_dev, const int32_t
                        int n_fft, int hop, const float* window,
                        const int32_t* band_lo, const int32_t* band_cnt, const int32_t* band_off, const float* band_w, const int32_t* lane_bands, int n_mels, int n_w,
                        float log_clamp, float* out, int64_t stride_b, int64_t stride_f, int64_t stride_m, void* stream);
+/* The gradient of ss_stft_logmel_fft with respect to the signals (csrc/mel_bwd.hip): g_y, laid out like y (every sample of every signal is written; with
+ * clip != 0 samples with |y| > 1 get 0), from the upstream gradient g_out[b * stride_b + f * stride_f + m * stride_m] (any strides; rows f >= a ragged
+ * signal's own frame count are filler and are not read).  The arguments up to n_w are the forward's; max_len = the longest signal (uniform_len for rows;
+ * host-known); hop a multiple of 4.  The transposed filterbank comes per bin: bin_band[513] = m0 | m1 << 8, the (at most two) bands with a non-zero
+ * weight over the bin, 255 = none, and bin_w[513][2] their weights; bin_taps = the largest number of bands over one bin (<= 2, checked).  One wave per
+ * frame recomputes the spectrum and writes the windowed frame gradient into workspace[B * F][1024] f32 (ss_stft_logmel_fft_backward_workspace_bytes);
+ * a second kernel sums, per sample, the frames that cover it and its reflections in a fixed order: no floating-point atomics, bitwise reproducible. */
+int64_t ss_stft_logmel_fft_backward_workspace_bytes(int B, int F); /* [host] */
+int ss_stft_logmel_fft_backward(const float* y, const int64_t* offsets_dev, const int32_t* lengths_dev, int64_t uniform_len, int64_t max_len, int B, int F, int pad,
+                                int clip, int n_fft, int hop, const float* window,
+                                const int32_t* band_lo, const int32_t* band_cnt, const int32_t* band_off, const float* band_w, const int32_t* lane_bands, int n_mels,
+                                int n_w, const int32_t* bin_band, const float* bin_w, int bin_taps, float log_clamp,
+                                const float* g_out, int64_t stride_b, int64_t stride_f, int64_t stride_m, float* workspace, int64_t workspace_bytes, float* g_y,
+                                void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Multi-head self-attention with learned relative-position logits (transformer.py:87-112 and

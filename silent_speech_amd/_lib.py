@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.environ.get('SS_AMD_LIBRARY') or os.path.join(_HERE, 'lib', 'libsilent_speech_hip.so')      # override: A/B runs of two builds on one box
 
 SS_F32, SS_BF16, SS_F64, SS_F32X3 = 0, 1, 2, 3
-ABI_VERSION = 16         # include/silent_speech_hip.h: SS_ABI_VERSION (struct layouts / signatures this binding was written against)
+ABI_VERSION = 17         # include/silent_speech_hip.h: SS_ABI_VERSION (struct layouts / signatures this binding was written against)
 OP_KC, OP_OC = 0, 1
 
 
@@ -128,9 +128,11 @@ SIGNATURES = {
     'ss_voc_tail': [_P, _P, _P, _P, _I, _L, _I, _I, _I, _F, _P],
     'ss_stft_magnitude': [_P, _L, _I, _P, _L, _I, _P],
     'ss_stft_logmel_fft': [_P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P, _L, _L, _L, _P],
+    'ss_stft_logmel_fft_backward': [_P, _P, _P, _L, _L, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _I, _F, _P, _L, _L, _L, _P, _L, _P, _P],
 }
 _LP = ctypes.POINTER(ctypes.c_int64)
-_HOST_FUNCS = {'ss_dtw_workspace_bytes': ([_I, _I, _LP, _LP, _LP], ctypes.c_int64),
+_HOST_FUNCS = {'ss_stft_logmel_fft_backward_workspace_bytes': ([_I, _I], ctypes.c_int64),
+               'ss_dtw_workspace_bytes': ([_I, _I, _LP, _LP, _LP], ctypes.c_int64),
                'ss_dtw_source': ([_I, _I, _L, _L], ctypes.c_int),
                'ss_bn_scratch_floats': ([_I, _I, _I], ctypes.c_int64),
                'ss_iir_filtfilt_workspace_bytes': ([_I, _I, _I], ctypes.c_int64),

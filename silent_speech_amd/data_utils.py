@@ -99,12 +99,18 @@ def _mel_basis(sampling_rate, n_fft, num_mels, fmin, fmax, device, ld):
 def mel_spectrogram(y, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, center=False):
     """y: (B, L) float32 in [-1, 1] on the GPU -> (B, num_mels, F) float32 log-mel, F = 1 + (L + n_fft - hop - n_fft)//hop.
     (The reference's min/max range warnings (:40-43) would force a device sync and are omitted.)  Dispatches through
-    torch.ops.silent_speech.stft_logmel (torch_ops.py)."""
+    torch.ops.silent_speech.stft_logmel (torch_ops.py).  With y.requires_grad the result is differentiable with respect to y (csrc/mel_bwd.hip) whenever the
+    direct FFT kernel takes the call: n_fft = 1024, center=False, win_size <= 1024, a filterbank that fits the kernel's tables and L > (n_fft - hop) / 2; its
+    value is the no-grad result bit for bit.  Every other configuration raises a ValueError at the call (no gradient exists for the DFT-GEMM formulation)."""
     if y.dim() != 2 or y.dtype != torch.float32:
         raise ValueError('y must be a float32 (B, L) tensor')
     if hop_size % 4 or n_fft % 4:
         raise ValueError('hop_size and n_fft must be multiples of 4 (16-byte f32 rows)')
     from . import torch_ops  # noqa: F401
+    if torch.is_grad_enabled() and y.requires_grad:
+        why = _not_differentiable(y.shape[1], n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, center, y.device)
+        if why:
+            raise ValueError('mel_spectrogram: y requires grad, but %s; only the n_fft = 1024, center=False path (the direct FFT kernel) is differentiable' % why)
     return torch.ops.silent_speech.stft_logmel(y, int(n_fft), int(num_mels), int(sampling_rate), int(hop_size), int(win_size), int(fmin), int(fmax), bool(center))
 
 
@@ -202,6 +208,131 @@ def _logmel_fft(y, offs, lens, uniform_len, B, F, pad, clip, n_fft, num_mels, sa
     return True
 
 
+_fft_bwd_cache = {}
+BWD_MAX_TAPS = 2          # csrc/mel_bwd.hip: bands with a non-zero weight over one bin
+
+
+def _fft_bwd_tables(n_fft, win_size, num_mels, sampling_rate, fmin, fmax, device):
+    """What ss_stft_logmel_fft_backward reads on top of _fft_tables: the TRANSPOSED filterbank per bin -- bin_band[513] = m0 | m1 << 8, the bands with a non-zero
+    weight over the bin (255 = none; a bin lies under at most two neighbouring Slaney triangles), bin_w[513][2] their weights -- and the largest number of
+    bands over one bin, which the launcher checks.  None when a bin lies under more than BWD_MAX_TAPS bands or the forward's tables do not fit."""
+    key = (n_fft, win_size, num_mels, sampling_rate, fmin, fmax, str(device))
+    if key not in _fft_bwd_cache:
+        tabs = None
+        if n_fft == 1024 and win_size <= n_fft and _fft_tables(n_fft, win_size, num_mels, sampling_rate, fmin, fmax, device) is not None:
+            basis = slaney_mel_filterbank(sampling_rate, n_fft, num_mels, fmin, fmax)
+            nb = n_fft // 2 + 1
+            band = np.full(nb, 255 | 255 << 8, dtype=np.int32)
+            w = np.zeros((nb, 2), dtype=np.float32)
+            taps = 0
+            for k in range(nb):
+                ms = np.nonzero(basis[:, k])[0]
+                taps = max(taps, len(ms))
+                if len(ms) <= BWD_MAX_TAPS:
+                    m = [int(x) for x in ms] + [255] * (2 - len(ms))
+                    band[k] = m[0] | m[1] << 8
+                    w[k, :len(ms)] = basis[ms, k]
+            if taps <= BWD_MAX_TAPS and num_mels < 255:
+                tabs = (torch.from_numpy(band).to(device), torch.from_numpy(w).to(device), taps)
+                _settle_cache(device)
+        _fft_bwd_cache[key] = tabs
+    return _fft_bwd_cache[key]
+
+
+def _not_differentiable(L, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, center, device):
+    """Why this configuration has no gradient (a phrase for the error message), or None when the direct FFT kernel and its backward take it."""
+    if center:
+        return 'center=True runs on the twice padded rows'
+    if n_fft != 1024 or win_size > n_fft:
+        return 'n_fft = %d / win_size = %d runs on the DFT-GEMM formulation' % (n_fft, win_size)
+    pad = int((n_fft - hop_size) / 2)
+    if L <= pad or L + 2 * pad < n_fft:
+        return 'a signal of %d samples is too short for the direct kernel (hop %d reflects %d samples)' % (L, hop_size, pad)
+    if _fft_bwd_tables(n_fft, win_size, num_mels, sampling_rate, fmin, fmax, device) is None:
+        return 'the filterbank (%d bands, %d Hz, %s .. %s Hz) does not fit the kernel\'s tables and runs on the DFT-GEMM formulation' % (num_mels, sampling_rate, fmin, fmax)
+    return None
+
+
+def _logmel_fft_backward(g, y, offs, lens, uniform_len, max_len, B, F, pad, clip, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, strides, g_y):
+    """One ss_stft_logmel_fft_backward call (csrc/mel_bwd.hip): g is the upstream gradient, read in place through strides = (signal, frame, band) in
+    elements; g_y has y's layout.  A configuration without a gradient is an error, never a fallback."""
+    tabs = _fft_tables(n_fft, win_size, num_mels, sampling_rate, fmin, fmax, y.device) if n_fft == 1024 and win_size <= n_fft else None
+    btabs = _fft_bwd_tables(n_fft, win_size, num_mels, sampling_rate, fmin, fmax, y.device)
+    if tabs is None or btabs is None:
+        raise ValueError('stft_logmel backward: n_fft = %d, win_size = %d, %d bands have no gradient; only the n_fft = 1024, center=False path is differentiable'
+                         % (n_fft, win_size, num_mels))
+    win, lo, cnt, boff, w, lb, n_w = tabs
+    bin_band, bin_w, taps = btabs
+    ws_bytes = _lib.lib().ss_stft_logmel_fft_backward_workspace_bytes(B, F)
+    ws = torch.empty(max(ws_bytes // 4, 1), dtype=torch.float32, device=y.device)
+    sb, sf, sm = strides
+    _lib.check(_lib.lib().ss_stft_logmel_fft_backward(_lib.ptr(y), _lib.ptr(offs) if offs is not None else None, _lib.ptr(lens) if lens is not None else None,
+                                                      int(uniform_len), int(max_len), B, F, pad, int(bool(clip)), n_fft, hop_size, _lib.ptr(win), _lib.ptr(lo),
+                                                      _lib.ptr(cnt), _lib.ptr(boff), _lib.ptr(w), _lib.ptr(lb), num_mels, n_w, _lib.ptr(bin_band), _lib.ptr(bin_w), taps,
+                                                      1e-5, _lib.ptr(g), sb, sf, sm, _lib.ptr(ws), ws_bytes, _lib.ptr(g_y), _lib.stream_of(y)),
+               'ss_stft_logmel_fft_backward')
+    return g_y
+
+
+def _mel_spectrogram_backward_impl(g, y, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, center):
+    """d loss / d y of mel_spectrogram's direct path from g = d loss / d mel (B, num_mels, F), any strides."""
+    B, L = y.shape
+    why = _not_differentiable(L, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, center, y.device)
+    if why:
+        raise ValueError('stft_logmel backward: %s; only the n_fft = 1024, center=False path is differentiable' % why)
+    y = y.contiguous()
+    pad = int((n_fft - hop_size) / 2)
+    F = 1 + (L + 2 * pad - n_fft) // hop_size
+    if tuple(g.shape) != (B, num_mels, F) or g.dtype != torch.float32 or g.device != y.device:
+        raise ValueError('stft_logmel backward: the upstream gradient must be a (%d, %d, %d) float32 tensor on the device of y' % (B, num_mels, F))
+    g_y = torch.empty_like(y)
+    return _logmel_fft_backward(g, y, None, None, L, L, B, F, pad, False, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax,
+                                (g.stride(0), g.stride(2), g.stride(1)), g_y)
+
+
+def _ragged_layout(flat, offsets, lengths, n_fft, hop_size):
+    """Host-side check of a ragged batch description before a kernel follows it: every signal lies inside the flat buffer and is longer than the reflected
+    stretch (one small device -> host copy).  Returns (lengths as a list, pad)."""
+    pad = int((n_fft - hop_size) / 2)
+    if flat.dim() != 1 or flat.dtype != torch.float32 or not flat.is_contiguous():
+        raise ValueError('stft_logmel_ragged: a flat contiguous float32 buffer is expected')
+    if offsets.dim() != 1 or lengths.shape != offsets.shape or offsets.dtype != torch.int64 or lengths.dtype != torch.int32 or offsets.shape[0] < 1 \
+            or offsets.device != flat.device or lengths.device != flat.device or not offsets.is_contiguous() or not lengths.is_contiguous():
+        raise ValueError('stft_logmel_ragged: offsets (B >= 1) int64 and lengths (B) int32, contiguous, on the device of the buffer')
+    if hop_size % 4 or hop_size <= 0:
+        raise ValueError('hop_size must be a positive multiple of 4')
+    o, n = offsets.cpu().tolist(), lengths.cpu().tolist()
+    for a, L in zip(o, n):
+        if a < 0 or a + L > flat.shape[0]:
+            raise ValueError('stft_logmel_ragged: signal [%d, %d) lies outside the buffer of %d samples' % (a, a + L, flat.shape[0]))
+        if L <= pad or L + 2 * pad < n_fft:
+            raise ValueError('signal too short for one frame')
+    return n, pad
+
+
+def _mel_ragged_impl(flat, offsets, lengths, F, clip, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax):
+    lens, pad = _ragged_layout(flat, offsets, lengths, n_fft, hop_size)
+    B = len(lens)
+    if F < max(1 + (L + 2 * pad - n_fft) // hop_size for L in lens):
+        raise ValueError('stft_logmel_ragged: F = %d is less than the longest signal\'s frame count' % F)
+    out = torch.empty(B, F, num_mels, dtype=torch.float32, device=flat.device)
+    if not _logmel_fft(flat, offsets, lengths, 0, B, F, pad, clip, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, out, frame_major=True):
+        raise ValueError('stft_logmel_ragged: n_fft = %d, win_size = %d, %d bands run on the DFT-GEMM formulation; only the n_fft = 1024 path is differentiable'
+                         % (n_fft, win_size, num_mels))
+    return out
+
+
+def _mel_ragged_backward_impl(g, flat, offsets, lengths, clip, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax):
+    """d loss / d flat from g = d loss / d buf (B, F, num_mels), any strides; samples of the buffer outside every signal get 0."""
+    lens, pad = _ragged_layout(flat, offsets, lengths, n_fft, hop_size)
+    B = len(lens)
+    if g.dim() != 3 or g.shape[0] != B or g.shape[2] != num_mels or g.dtype != torch.float32 or g.device != flat.device:
+        raise ValueError('stft_logmel_ragged backward: the upstream gradient must be a (%d, F, %d) float32 tensor on the device of the buffer' % (B, num_mels))
+    g_y = torch.zeros_like(flat)
+    return _logmel_fft_backward(g, flat, offsets, lengths, 0, max(lens), B, int(g.shape[1]), pad, clip, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax,
+                                (g.stride(0), g.stride(1), g.stride(2)), g_y)
+
+
 def _stft_logmel(ypad, B, F, ldp, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, out, frame_major):
     """padded signals [B][ldp] -> log-mel of frames 0..F-1 of every row: the GEMM formulation (any n_fft): two f32 GEMMs (windowed DFT matrix, mel basis)
     around the magnitude kernel.  frame_major: out is [B*F][num_mels] (frames of a signal are contiguous rows) instead of the reference's (B, num_mels, F)."""
@@ -229,7 +360,10 @@ def mel_spectrogram_batch(signals, n_fft=1024, num_mels=80, sampling_rate=22050,
     padded buffer = utterances, RowMap batch stride), magnitude, one mel GEMM with the log-clamp epilogue.
     signals: list of 1-D f32 device tensors at `sampling_rate`, or the pair (flat f32 device tensor holding them back to back, lengths) -- what
     a loader that uploaded the whole batch in one copy has.  Returns (buf [B][F_max][num_mels] f32, frames per utterance):
-    utterance b's `pytorch_mspec.squeeze(0).T` is buf[b, :frames[b]] -- a contiguous view, no per-utterance copy."""
+    utterance b's `pytorch_mspec.squeeze(0).T` is buf[b, :frames[b]] -- a contiguous view, no per-utterance copy.
+    When grad is enabled and the flat buffer or any listed signal requires grad, the call goes through torch.ops.silent_speech.stft_logmel_ragged and buf
+    carries a grad_fn (csrc/mel_bwd.hip; n_fft = 1024 only, anything else raises a ValueError); otherwise the code path below runs as before.  The rows
+    buf[b, frames[b]:] are filler: they contribute no gradient, whatever the upstream gradient holds there."""
     if hop_size % 4 or n_fft % 4:
         raise ValueError('hop_size and n_fft must be multiples of 4 (16-byte f32 rows)')
     packed = isinstance(signals, tuple)
@@ -251,6 +385,14 @@ def mel_spectrogram_batch(signals, n_fft=1024, num_mels=80, sampling_rate=22050,
     ldp = (max(lens) + 2 * pad + 3) // 4 * 4
     offs_d = torch.from_numpy(offs).to(dev, non_blocking=True)
     lens_d = torch.from_numpy(np.asarray(lens, dtype=np.int32)).to(dev, non_blocking=True)
+    if torch.is_grad_enabled() and flat.requires_grad:                 # (a listed signal that requires grad makes the concatenation require it)
+        why = _not_differentiable(min(lens), n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, False, dev)
+        if why:
+            raise ValueError('mel_spectrogram_batch: the signals require grad, but %s; only the n_fft = 1024 path (the direct FFT kernel) is differentiable' % why)
+        from . import torch_ops  # noqa: F401
+        buf = torch.ops.silent_speech.stft_logmel_ragged(flat, offs_d, lens_d, F, bool(clip), int(n_fft), int(num_mels), int(sampling_rate), int(hop_size),
+                                                         int(win_size), int(fmin), int(fmax))
+        return buf, frames
     out = torch.empty(B, F, num_mels, dtype=torch.float32, device=dev)
     if _logmel_fft(flat, offs_d, lens_d, 0, B, F, pad, clip, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, out, frame_major=True):
         return out, frames

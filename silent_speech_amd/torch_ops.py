@@ -8,7 +8,8 @@
     ctc_beam_search                  the search of recognition_model.py:33-35,48-49: CTC prefix beam search + label n-gram table, one launch per batch (inference only)
     ctc_word_beam_search             the same search confined to a lexicon, a word n-gram with backoff scored at every word end (WordNgramLM), inference only
     word_ngram_score                 ln P(w | w2, w1) of word triples by the device function of that search (tests, n-best rescoring)
-    stft_logmel                      data_utils.py:39-62
+    stft_logmel / stft_logmel_backward                 data_utils.py:39-62 and its gradient with respect to the audio (csrc/mel_bwd.hip)
+    stft_logmel_ragged / stft_logmel_ragged_backward   the same pair for a ragged batch in one flat buffer (load_audio's clip included)
     emg_features                     data_utils.py:85-136 (get_emg_features; no autograd: the reference's features are numpy)
     audio_resample / audio_level     the band-limited resample (:75) and normalize_volume's levels (:19-27) of load_audio for a ragged batch of stored audio
     spectral_gate_profile / spectral_gate      the stationary noise gate of data_collection/clean_audio.py:53 (noisereduce's reduce_noise) for a ragged batch
@@ -409,6 +410,74 @@ def _(y, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, center)
     return y.new_empty(y.shape[0], num_mels, 1 + (Lp - n_fft) // hop_size)
 
 
+@torch.library.custom_op('silent_speech::stft_logmel_backward', mutates_args=())
+def stft_logmel_backward(g: Tensor, y: Tensor, n_fft: int, num_mels: int, sampling_rate: int, hop_size: int, win_size: int, fmin: int, fmax: int, center: bool) -> Tensor:
+    """d loss / d y (B, L) of stft_logmel from g = d loss / d mel (B, num_mels, F), read through its strides (csrc/mel_bwd.hip).  Only the direct FFT path
+    (n_fft = 1024, center=False) has a gradient: anything else raises.  No autograd formula of its own (no second derivative)."""
+    from .data_utils import _mel_spectrogram_backward_impl
+    return _mel_spectrogram_backward_impl(g, y, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, center)
+
+
+@stft_logmel_backward.register_fake
+def _(g, y, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, center):
+    return y.new_empty(y.shape)
+
+
+def _stft_logmel_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0])
+    ctx.params = tuple(inputs[1:])
+
+
+def _stft_logmel_bwd(ctx, g):
+    y, = ctx.saved_tensors
+    return (torch.ops.silent_speech.stft_logmel_backward(g, y, *ctx.params),) + (None,) * 8
+
+
+stft_logmel.register_autograd(_stft_logmel_bwd, setup_context=_stft_logmel_setup)
+
+
+@torch.library.custom_op('silent_speech::stft_logmel_ragged', mutates_args=())
+def stft_logmel_ragged(flat: Tensor, offsets: Tensor, lengths: Tensor, F: int, clip: bool, n_fft: int, num_mels: int, sampling_rate: int, hop_size: int,
+                       win_size: int, fmin: int, fmax: int) -> Tensor:
+    """load_audio's clip (when `clip`) + mel_spectrogram(center=False) of a ragged batch: signal b = flat[offsets[b] .. + lengths[b]) (offsets int64, lengths
+    int32, on the device) -> buf (B, F, num_mels) f32, F >= the longest signal's frame count; rows behind a signal's own frames are filler.  n_fft = 1024
+    only (the direct FFT kernel); differentiable with respect to flat."""
+    from .data_utils import _mel_ragged_impl
+    return _mel_ragged_impl(flat, offsets, lengths, F, clip, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax)
+
+
+@stft_logmel_ragged.register_fake
+def _(flat, offsets, lengths, F, clip, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax):
+    return flat.new_empty((offsets.shape[0], F, num_mels))
+
+
+@torch.library.custom_op('silent_speech::stft_logmel_ragged_backward', mutates_args=())
+def stft_logmel_ragged_backward(g: Tensor, flat: Tensor, offsets: Tensor, lengths: Tensor, clip: bool, n_fft: int, num_mels: int, sampling_rate: int,
+                                hop_size: int, win_size: int, fmin: int, fmax: int) -> Tensor:
+    """d loss / d flat of stft_logmel_ragged from g = d loss / d buf (B, F, num_mels), any strides: filler rows are not read, samples outside every signal
+    get 0, with `clip` samples beyond [-1, 1] get 0.  No autograd formula of its own."""
+    from .data_utils import _mel_ragged_backward_impl
+    return _mel_ragged_backward_impl(g, flat, offsets, lengths, clip, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax)
+
+
+@stft_logmel_ragged_backward.register_fake
+def _(g, flat, offsets, lengths, clip, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax):
+    return flat.new_empty(flat.shape)
+
+
+def _stft_logmel_ragged_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0], inputs[1], inputs[2])
+    ctx.params = tuple(inputs[4:])
+
+
+def _stft_logmel_ragged_bwd(ctx, g):
+    flat, offsets, lengths = ctx.saved_tensors
+    return (torch.ops.silent_speech.stft_logmel_ragged_backward(g, flat, offsets, lengths, *ctx.params),) + (None,) * 11
+
+
+stft_logmel_ragged.register_autograd(_stft_logmel_ragged_bwd, setup_context=_stft_logmel_ragged_setup)
+
+
 # ------------------------------------------------------------------------------------------------ emg_features
 @torch.library.custom_op('silent_speech::emg_features', mutates_args=())
 def emg_features(x: Tensor) -> Tensor:
@@ -618,5 +687,6 @@ def _(x, w, k, slope):
     return x.new_empty((x.shape[0],))
 
 
-OPS = ('model_forward', 'model_forward_ragged', 'model_backward', 'dtw_loss', 'dtw_align', 'ctc_loss', 'ctc_beam_search', 'ctc_word_beam_search', 'word_ngram_score', 'stft_logmel', 'emg_features', 'audio_resample', 'audio_level', 'spectral_gate_profile', 'spectral_gate', 'fused_adamw',
+OPS = ('model_forward', 'model_forward_ragged', 'model_backward', 'dtw_loss', 'dtw_align', 'ctc_loss', 'ctc_beam_search', 'ctc_word_beam_search', 'word_ngram_score', 'stft_logmel', 'stft_logmel_backward', 'stft_logmel_ragged', 'stft_logmel_ragged_backward',
+       'emg_features', 'audio_resample', 'audio_level', 'spectral_gate_profile', 'spectral_gate', 'fused_adamw',
        'vocoder_conv1d', 'vocoder_conv_transpose1d', 'vocoder_tail')
