@@ -30,9 +30,9 @@ extern "C" {
 const char* ss_last_error(void);
 /* Library/ABI version and the GPU architecture the kernels were compiled for ("gfx950"). */
 /* Bumped whenever a struct layout or an entry-point signature changes (3: ss_gemm_epilogue column-statistics fields, the plan /
- * attention-image / LayerNorm-workspace entry points, ss_dtw_cumulative; 4: ss_loss_index_tables; 5: gate recomputation arguments of ss_bn_backward_sums / ss_bn_backward_apply; 7: ss_split_planes / ss_gemm_planes, ss_dw_job.flags, up to 24 jobs per grouped launch; 8: ss_stft_logmel_fft, the rejected-frame counter behind the matrix of ss_phoneme_confusion; 9: planes_hi / planes_lo / planes_only of ss_gemm_epilogue, dropout groups of the GEMM epilogue are row-major; 10: ss_emg_features_batch; 11: the ss_voc_* vocoder entry points; 12: the ragged-batch inference entry points ss_bn_apply_ragged, ss_relpos_attention_forward_ragged, ss_plan_forward_ragged; 13: ss_ctc_beam_search / ss_ctc_beam_workspace_bytes; 14: ss_word_lm, ss_ctc_word_beam_search / ss_ctc_word_beam_workspace_bytes, ss_word_ngram_score; 15: ss_audio_resample_batch / ss_audio_resample_supported / ss_audio_resample_limits, ss_audio_level_batch; 16: ss_spectral_gate_profile / ss_spectral_gate_batch / ss_spectral_gate_limits; 17: ss_stft_logmel_fft_backward / ss_stft_logmel_fft_backward_workspace_bytes).  Bindings must compare it with SS_ABI_VERSION at load time: a stale
+ * attention-image / LayerNorm-workspace entry points, ss_dtw_cumulative; 4: ss_loss_index_tables; 5: gate recomputation arguments of ss_bn_backward_sums / ss_bn_backward_apply; 7: ss_split_planes / ss_gemm_planes, ss_dw_job.flags, up to 24 jobs per grouped launch; 8: ss_stft_logmel_fft, the rejected-frame counter behind the matrix of ss_phoneme_confusion; 9: planes_hi / planes_lo / planes_only of ss_gemm_epilogue, dropout groups of the GEMM epilogue are row-major; 10: ss_emg_features_batch; 11: the ss_voc_* vocoder entry points; 12: the ragged-batch inference entry points ss_bn_apply_ragged, ss_relpos_attention_forward_ragged, ss_plan_forward_ragged; 13: ss_ctc_beam_search / ss_ctc_beam_workspace_bytes; 14: ss_word_lm, ss_ctc_word_beam_search / ss_ctc_word_beam_workspace_bytes, ss_word_ngram_score; 15: ss_audio_resample_batch / ss_audio_resample_supported / ss_audio_resample_limits, ss_audio_level_batch; 16: ss_spectral_gate_profile / ss_spectral_gate_batch / ss_spectral_gate_limits; 17: ss_stft_logmel_fft_backward / ss_stft_logmel_fft_backward_workspace_bytes; 18: ss_ctc_align / ss_ctc_align_workspace_bytes).  Bindings must compare it with SS_ABI_VERSION at load time: a stale
  * library paired with newer headers would otherwise read garbage struct fields instead of failing. */
-#define SS_ABI_VERSION 17
+#define SS_ABI_VERSION 18
 int ss_abi_version(void);
 const char* ss_target_arch(void);
 
@@ -425,6 +425,36 @@ int ss_ctc_word_beam_search(const float* logits, int64_t ld, int V, int blank, i
 /* out[i] = ln P(w | w2, w1) of triples[i] = (w2, w1, w) (device, int32 x3) by the device function the search uses; an id outside the tables
  * (w not in [0, n_uni), w1 / w2 not in [-1, n_uni)) gives NaN. */
 int ss_word_ngram_score(const ss_word_lm* lm, const int32_t* triples, int64_t n, float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Forced alignment: the best (Viterbi) alignment of a KNOWN label string to the frame posteriors, the whole batch in one launch
+ * (csrc/ctc_align.hip; what torchaudio.functional.forced_align computes for one utterance).
+ * Inputs: f32 logits (rows, ld), classes in columns 0 .. V-1 (V <= 4096, ld >= V, further columns are never read); lse = per-frame log-sum-exp
+ * (ss_frame_lse with col0 = 0); utt_dev (device, int64 x4 per utterance) = first frame, frames T, first target index, target length S -- the
+ * packed layout and the slot layout of ss_plan_forward_ragged alike; frames behind an utterance's end and rows between utterances are never
+ * read.  targets: flat int32, n_targets of them; y = the S labels of the utterance.  total_frames >= the sum of the frames (it sizes the
+ * workspace; an utterance that would exceed it, or leave [0, rows), is cut short, never read out of bounds).  S <= max_target_len <= 511.
+ * Definition: logp_t(c) = logit_t(c) - lse_t, natural log, f32.
+ *   CTC topology (blank in [0, V)): extended states s = 0 .. 2S, even = blank, odd s = token (s-1)/2.  d_0(0) = logp_0(blank), d_0(1) =
+ *     logp_0(y_0), every other state -inf.  d_t(s) = best + logp_t(label(s)), best over d_{t-1}(s), d_{t-1}(s-1) and -- only if s is a token
+ *     state and its label differs from the previous token's -- d_{t-1}(s-2).  A predecessor of -inf is no candidate; if none exists,
+ *     d_t(s) = -inf.  The sum is ONE f32 addition best + (logit - lse) per step (no rescaling, no reassociation), so an f32 restatement
+ *     reproduces the score.  score = max(d_{T-1}(2S-1), d_{T-1}(2S)).
+ *   ties: among equal predecessors the smallest jump wins (stay, then s-1, then s-2); at the end d_{T-1}(2S-1) wins over an equal d_{T-1}(2S).
+ *   linear topology (blank = -1, heads without a blank class): the states are the S tokens, predecessors s and s-1, start in token 0, end in
+ *     token S-1, same tie rule.
+ *   T = 0 and S = 0: score 0.  S = 0, T > 0: all blank under CTC, -inf under linear.  No alignment (too few frames, repeats without room for
+ *     their blanks): -inf.  A label outside [0, V) or equal to the blank, or a table entry whose targets leave [0, n_targets) or exceed
+ *     max_target_len: -inf, and nothing is indexed out of bounds.  A score that is not > -inf (NaN logits) is reported as -inf.
+ * Outputs: score (n_utt) f32; frame_token (rows) int32 = token index within the utterance's target, -1 blank, -2 for rows of no utterance and
+ * for every frame of an utterance of score -inf; parallel to targets: token_first (frame relative to the utterance's first), token_frames,
+ * token_logp (f32 sum of logp over the token's frames, ascending) -- -1 / 0 / 0 for score -inf; entries of no utterance are not written.
+ * workspace: ss_ctc_align_workspace_bytes(n_utt, total_frames, max_target_len) bytes (2-bit back-pointers, 256 bytes per frame; needs no
+ * initialisation); -1 = bad arguments. */
+int64_t ss_ctc_align_workspace_bytes(int n_utt, int64_t total_frames, int max_target_len);
+int ss_ctc_align(const float* logits, int64_t ld, int V, int blank, int64_t rows, const float* lse, const int64_t* utt_dev, int n_utt,
+                 int64_t total_frames, int max_target_len, const int32_t* targets, int64_t n_targets, void* workspace, float* score,
+                 int32_t* frame_token, int32_t* token_first, int32_t* token_frames, float* token_logp, void* stream);
 
 /* AdamW over a flat f32 arena (transduction_model.py:178,210).  step is 1-based. */
 int ss_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,

@@ -7,6 +7,9 @@
     LabelNgramLM                             label trigram table counted from text, the language model of the beam search
     WordNgramLM                              word n-gram with backoff (orders 1 .. 3, from ARPA text or counted from transcripts) + the lexicon of
                                              its vocabulary: beam_decode* with it run the lexicon-constrained search of csrc/ctc_word_decode.hip
+    forced_align(logits, lengths, targets)   best alignment of KNOWN label strings to the frames on the device (csrc/ctc_align.hip): Alignment per
+                                             utterance; forced_align_utterances for the list Model.forward_utterances returns
+    word_segments(alignment, text_int, tt)   (word, start_s, end_s, confidence) of a character alignment; align(model, testset, device) for a data set
     test(model, testset, device)             :30-58 -> WER; decoder='greedy' (default) or 'beam'
     train_model(trainset, devset, device)    :61-117 (AdamW, warm-up, x2 gradient accumulation, MultiStepLR)
 
@@ -20,6 +23,7 @@ read from ARPA text or counted from transcripts; the search is lexicon-constrain
 KenLM BINARY format (third-party C++; convert lm.binary to ARPA text) and parity with ctcdecode's own numbers, which stays unpinned because
 ctcdecode is not available to compare against.  test() reports greedy WER by default and beam-search WER with decoder='beam'.
 """
+import collections
 import logging
 import os
 import string
@@ -560,6 +564,120 @@ def beam_decode_utterances(logits, *, beam_width=100, n_best=1, lm=None, alpha=0
             any(y._base is not head or y.shape[1] != V or y.storage_offset() != b * T * head.shape[1] for b, y in enumerate(logits)):
         raise ValueError('beam_decode_utterances takes the list Model.forward_utterances returned')
     return _beam_search(head, V, V - 1, [b * T for b in range(B)], [int(y.shape[0]) for y in logits], beam_width, n_best, lm, alpha, beta, space)
+
+
+Alignment = collections.namedtuple('Alignment', ['score', 'frames', 'token_first', 'token_frames', 'token_logp'])
+Alignment.__doc__ = """Best alignment of one utterance's label string to its frames (ss_ctc_align in include/silent_speech_hip.h): score (float, natural log;
+-inf = no alignment exists), frames (T,) int32 = index of the token a frame belongs to, -1 for blank (all -2 without an alignment), and per token its
+first frame, its frame count and the sum of the log-probabilities of its frames ((S,) int32, int32, float32; -1 / 0 / 0 without an alignment)."""
+MAX_ALIGN_TARGET = 511
+FRAME_SECONDS = 256 / 22050          # one output frame of the model = 8 raw samples at 689.06 Hz = the mel hop
+
+
+def _forced_align(name, head, V, blank, topology, first, frames, targets):
+    """One table upload, lse + alignment launches, one read-back.  head: (M, ld) f32 on the device; first / frames: per utterance, host ints."""
+    if topology not in ('ctc', 'linear'):
+        raise ValueError("%s: topology is 'ctc' or 'linear'" % name)
+    n = len(frames)
+    if len(targets) != n:
+        raise ValueError('%s: %d target strings for %d utterances' % (name, len(targets), n))
+    ys = [np.asarray(y.detach().cpu() if isinstance(y, torch.Tensor) else y, dtype=np.int64).reshape(-1) for y in targets]
+    blank = -1 if topology == 'linear' else int(blank)
+    if topology == 'ctc' and not (0 <= blank < V):
+        raise ValueError('%s: blank %d is not one of the %d classes' % (name, blank, V))
+    for b, y in enumerate(ys):
+        if y.size > MAX_ALIGN_TARGET:
+            raise ValueError('%s: target %d has %d labels (at most %d)' % (name, b, y.size, MAX_ALIGN_TARGET))
+        if y.size and (y.min() < 0 or y.max() >= V or (y == blank).any()):
+            raise ValueError('%s: target %d has a label outside [0, %d) or equal to the blank %d' % (name, b, V, blank))
+    if n == 0:
+        return []
+    S = [int(y.size) for y in ys]
+    tfirst = np.concatenate([[0], np.cumsum(S)])[:-1]
+    table = np.stack([np.asarray(first, dtype=np.int64), np.asarray(frames, dtype=np.int64), tfirst.astype(np.int64), np.asarray(S, dtype=np.int64)], 1)
+    flat = np.concatenate(ys + [np.zeros(1, dtype=np.int64)]).astype(np.int32)          # one spare entry: never an empty upload
+    utt, tg = staging.upload([table, flat], head.device)
+    score, frame_token, token_first, token_frames, token_logp = torch.ops.silent_speech.ctc_forced_align(
+        head, utt, tg, V, blank, int(sum(frames)), max(S))
+    back = torch.cat([score.view(torch.int32), frame_token, token_first, token_frames, token_logp.view(torch.int32)]).cpu().numpy()       # ONE read-back
+    M, nt = frame_token.shape[0], flat.shape[0]
+    score, frame_token = back[:n].view(np.float32), back[n:n + M]
+    token_first, token_frames, token_logp = back[n + M:n + M + nt], back[n + M + nt:n + M + 2 * nt], back[n + M + 2 * nt:].view(np.float32)
+    return [Alignment(float(score[b]), frame_token[first[b]:first[b] + frames[b]].copy(), token_first[tfirst[b]:tfirst[b] + S[b]].copy(),
+                      token_frames[tfirst[b]:tfirst[b] + S[b]].copy(), token_logp[tfirst[b]:tfirst[b] + S[b]].copy()) for b in range(n)]
+
+
+def forced_align(pred, lengths, targets, blank=None, *, topology='ctc'):
+    """Best (Viterbi) alignment of known label strings to packed logits (rows, T, V) (NOT log-softmaxed), utterances back to back with `lengths`
+    frames each, in one launch on the device.  targets: a list of int lists or tensors, one per utterance; blank defaults to V - 1.
+    topology='linear' aligns without a blank (heads that have none, such as the transduction model's phoneme head): every frame belongs to a token.
+    Returns a list of Alignment; an utterance no alignment exists for (too few frames, repeated labels without room for the blank between them)
+    has score -inf.  Raises ValueError for lengths that do not fit, a target longer than 511 or a label outside [0, V) or equal to the blank."""
+    B, T, V = pred.shape
+    blank = V - 1 if blank is None else int(blank)
+    frames = [int(n) for n in lengths]
+    if sum(frames) > B * T or any(n < 0 for n in frames):
+        raise ValueError('forced_align: the lengths do not fit the %d packed frames' % (B * T))
+    first = [int(f) for f in np.concatenate([[0], np.cumsum(frames)])[:-1]] if frames else []
+    if topology not in ('ctc', 'linear'):
+        raise ValueError("forced_align: topology is 'ctc' or 'linear'")
+    return _forced_align('forced_align', pred.reshape(B * T, V).float().contiguous(), V, blank, topology, first, frames, targets)
+
+
+def forced_align_utterances(logits, targets, *, topology='ctc'):
+    """forced_align for the per-utterance logits Model.forward_utterances returns -- (T_b, V) views of ONE (B T_max, >= V) head buffer --: the
+    slots are read in place (first frame b T_max, T_b frames; filler rows and columns are never looked at).  blank = V - 1."""
+    if not logits:
+        return []
+    head, V = logits[0]._base, logits[0].shape[1]
+    B, T = len(logits), max(int(y.shape[0]) for y in logits)
+    if head is None or head.dim() != 2 or head.dtype != torch.float32 or not head.is_contiguous() or head.shape[0] != B * T or \
+            any(y._base is not head or y.shape[1] != V or y.storage_offset() != b * T * head.shape[1] for b, y in enumerate(logits)):
+        raise ValueError('forced_align_utterances takes the list Model.forward_utterances returned')
+    return _forced_align('forced_align_utterances', head, V, V - 1, topology, [b * T for b in range(B)], [int(y.shape[0]) for y in logits], targets)
+
+
+def word_segments(alignment, text_int, text_transform, frame_seconds=FRAME_SECONDS):
+    """Word time stamps of an Alignment of the character string text_int: a list of (word, start_s, end_s, confidence).  A word is a maximal run
+    of non-space characters; it starts at the first frame of its first character and ends behind the last frame of its last character (blanks
+    between its characters are inside it; spaces and the blanks around them belong to no word); confidence = exp(sum of its characters'
+    token_logp / sum of their frames), the geometric mean of the frame posteriors along the path.  No alignment (score -inf): []."""
+    ints = [int(c) for c in (text_int.tolist() if hasattr(text_int, 'tolist') else text_int)]
+    if not alignment.score > -np.inf:
+        return []
+    if len(ints) != len(alignment.token_first):
+        raise ValueError('word_segments: %d characters, but the alignment has %d tokens' % (len(ints), len(alignment.token_first)))
+    space = text_transform.chars.index(' ')
+    words, run = [], []
+    for k, c in enumerate(ints + [space]):
+        if c != space:
+            run.append(k)
+        elif run:
+            a, z = run[0], run[-1]
+            logp = float(np.sum(alignment.token_logp[a:z + 1], dtype=np.float64))
+            nfr = int(np.sum(alignment.token_frames[a:z + 1]))
+            words.append((text_transform.int_to_text(ints[a:z + 1]), int(alignment.token_first[a]) * frame_seconds,
+                          int(alignment.token_first[z] + alignment.token_frames[z]) * frame_seconds, float(np.exp(logp / max(nfr, 1)))))
+            run = []
+    return words
+
+
+def align(model, testset, device, *, batch_size=8):
+    """Word time stamps of every example of testset against its own transcript: eval-mode Model.forward_utterances in groups of batch_size whole
+    utterances, forced_align_utterances against each example's text_int, word_segments per utterance.  Returns one list of
+    (word, start_s, end_s, confidence) per example ([] where the transcript does not fit the utterance's frames)."""
+    model.eval()
+    tt = testset.text_transform
+    out = []
+    with torch.no_grad():
+        for first in range(0, len(testset), batch_size):
+            group = [testset[i] for i in range(first, min(first + batch_size, len(testset)))]
+            logits = model.forward_utterances([ex['raw_emg'].to(dtype=torch.float32) for ex in group])
+            texts = [torch.as_tensor(ex['text_int']).tolist() for ex in group]
+            for al, text in zip(forced_align_utterances(logits, texts), texts):
+                out.append(word_segments(al, text, tt))
+    model.train()
+    return out
 
 
 def test(model, testset, device, *, batch_size=1, whole_utterances=False, decoder='greedy', beam_width=100, lm=None, alpha=0.0, beta=0.0):

@@ -7,6 +7,7 @@
     ctc_loss                         recognition_model.py:96-101
     ctc_beam_search                  the search of recognition_model.py:33-35,48-49: CTC prefix beam search + label n-gram table, one launch per batch (inference only)
     ctc_word_beam_search             the same search confined to a lexicon, a word n-gram with backoff scored at every word end (WordNgramLM), inference only
+    ctc_forced_align                 best alignment of known label strings to the frame posteriors (CTC or blank-free linear topology), frame labels and token spans, one launch per batch (inference only)
     word_ngram_score                 ln P(w | w2, w1) of word triples by the device function of that search (tests, n-best rescoring)
     stft_logmel / stft_logmel_backward                 data_utils.py:39-62 and its gradient with respect to the audio (csrc/mel_bwd.hip)
     stft_logmel_ragged / stft_logmel_ragged_backward   the same pair for a ragged batch in one flat buffer (load_audio's clip included)
@@ -378,6 +379,57 @@ def _(logits, utt, V, blank, space, total_frames, max_len, beam_width, n_best, l
             logits.new_empty((n, n_best)), logits.new_empty((n, n_best)), logits.new_empty((n, n_best), dtype=torch.int32))
 
 
+# ------------------------------------------------------------------------------------------------ ctc_forced_align (inference only: no autograd)
+@torch.library.custom_op('silent_speech::ctc_forced_align', mutates_args=())
+def ctc_forced_align(logits: Tensor, utt: Tensor, targets: Tensor, V: int, blank: int, total_frames: int,
+                     max_target_len: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """Best alignment of known label strings to the frame posteriors (ss_ctc_align in include/silent_speech_hip.h states the definition and the
+    ties).  logits [M][ld >= V] f32 raw model outputs; utt [n][4] int64 on the device = (first frame, frames, first target index, target length)
+    per utterance, packed or slot layout; targets flat int32; blank in [0, V), or -1 for the linear topology of a head without a blank;
+    total_frames >= the sum of the frames, max_target_len >= the longest target (<= 511).
+    Returns (score [n] f32, frame_token [M] int32: token index, -1 blank, -2 no utterance / no alignment, and parallel to targets token_first,
+    token_frames int32 and token_logp f32: -1 / 0 / 0 where no alignment exists)."""
+    dev = logits.device
+    if logits.dim() != 2 or logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise RuntimeError('ctc_forced_align: logits must be a contiguous (frames, ld) float32 matrix')
+    if utt.dim() != 2 or utt.shape[1] != 4 or utt.dtype != torch.int64 or not utt.is_contiguous() or utt.device != dev:
+        raise RuntimeError('ctc_forced_align: utt must be a contiguous (n, 4) int64 table on the device of the logits')
+    if targets.dim() != 1 or targets.dtype != torch.int32 or not targets.is_contiguous() or targets.device != dev:
+        raise RuntimeError('ctc_forced_align: targets must be a contiguous flat int32 tensor on the device of the logits')
+    # everything the launches below rely on is checked HERE: ss_frame_lse reads V columns at stride ld whatever it is told
+    if not (1 <= V <= min(logits.shape[1], 4096)) or not (-1 <= blank < V):
+        raise RuntimeError('ctc_forced_align: %d classes (1 .. min(row stride %d, 4096)), blank %d (-1: linear topology)' % (V, logits.shape[1], blank))
+    if not (0 <= max_target_len <= 511) or total_frames < 0:
+        raise RuntimeError('ctc_forced_align: max_target_len %d (0 .. 511), total_frames %d' % (max_target_len, total_frames))
+    M, ld = logits.shape
+    n, nt = utt.shape[0], targets.shape[0]
+    st = _lib.stream_of(logits)
+    ws_bytes = _L().ss_ctc_align_workspace_bytes(n, total_frames, max_target_len)
+    if ws_bytes < 0:
+        raise RuntimeError('ctc_forced_align: max_target_len %d (0 .. 511)' % max_target_len)
+    lse = torch.empty(max(M, 1), dtype=torch.float32, device=dev)
+    amax = torch.empty(max(M, 1), dtype=torch.int32, device=dev)
+    if M:
+        _lib.check(_L().ss_frame_lse(_p(logits), ld, 0, V, M, _p(lse), _p(amax), st), 'ss_frame_lse')
+    ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device=dev)
+    score = torch.empty(n, dtype=torch.float32, device=dev)
+    frame_token = torch.empty(M, dtype=torch.int32, device=dev)
+    token_first = torch.empty(nt, dtype=torch.int32, device=dev)
+    token_frames = torch.empty(nt, dtype=torch.int32, device=dev)
+    token_logp = torch.empty(nt, dtype=torch.float32, device=dev)
+    _lib.check(_L().ss_ctc_align(_p(logits), ld, V, blank, M, _p(lse), _p(utt) if n else None, n, total_frames, max_target_len,
+                                 _p(targets) if nt else None, nt, _p(ws), _p(score) if n else None, _p(frame_token) if M else None,
+                                 _p(token_first) if nt else None, _p(token_frames) if nt else None, _p(token_logp) if nt else None, st), 'ss_ctc_align')
+    return score, frame_token, token_first, token_frames, token_logp
+
+
+@ctc_forced_align.register_fake
+def _(logits, utt, targets, V, blank, total_frames, max_target_len):
+    n, nt = utt.shape[0], targets.shape[0]
+    return (logits.new_empty((n,)), logits.new_empty((logits.shape[0],), dtype=torch.int32), logits.new_empty((nt,), dtype=torch.int32),
+            logits.new_empty((nt,), dtype=torch.int32), logits.new_empty((nt,)))
+
+
 @torch.library.custom_op('silent_speech::word_ngram_score', mutates_args=())
 def word_ngram_score(triples: Tensor, uni: Tensor, bi_keys: Tensor, bi_val: Tensor, tri_keys: Tensor, tri_val: Tensor, bi_probe: int, tri_probe: int) -> Tensor:
     """ln P(w | w2, w1) of every row (w2, w1, w) of triples [n][3] int32 (-1 = no such context word) by the backoff rule of ss_word_lm, with the
@@ -687,6 +739,6 @@ def _(x, w, k, slope):
     return x.new_empty((x.shape[0],))
 
 
-OPS = ('model_forward', 'model_forward_ragged', 'model_backward', 'dtw_loss', 'dtw_align', 'ctc_loss', 'ctc_beam_search', 'ctc_word_beam_search', 'word_ngram_score', 'stft_logmel', 'stft_logmel_backward', 'stft_logmel_ragged', 'stft_logmel_ragged_backward',
+OPS = ('model_forward', 'model_forward_ragged', 'model_backward', 'dtw_loss', 'dtw_align', 'ctc_loss', 'ctc_beam_search', 'ctc_word_beam_search', 'ctc_forced_align', 'word_ngram_score', 'stft_logmel', 'stft_logmel_backward', 'stft_logmel_ragged', 'stft_logmel_ragged_backward',
        'emg_features', 'audio_resample', 'audio_level', 'spectral_gate_profile', 'spectral_gate', 'fused_adamw',
        'vocoder_conv1d', 'vocoder_conv_transpose1d', 'vocoder_tail')
