@@ -30,9 +30,9 @@ extern "C" {
 const char* ss_last_error(void);
 /* Library/ABI version and the GPU architecture the kernels were compiled for ("gfx950"). */
 /* Bumped whenever a struct layout or an entry-point signature changes (3: ss_gemm_epilogue column-statistics fields, the plan /
- * attention-image / LayerNorm-workspace entry points, ss_dtw_cumulative; 4: ss_loss_index_tables; 5: gate recomputation arguments of ss_bn_backward_sums / ss_bn_backward_apply; 7: ss_split_planes / ss_gemm_planes, ss_dw_job.flags, up to 24 jobs per grouped launch; 8: ss_stft_logmel_fft, the rejected-frame counter behind the matrix of ss_phoneme_confusion; 9: planes_hi / planes_lo / planes_only of ss_gemm_epilogue, dropout groups of the GEMM epilogue are row-major; 10: ss_emg_features_batch; 11: the ss_voc_* vocoder entry points; 12: the ragged-batch inference entry points ss_bn_apply_ragged, ss_relpos_attention_forward_ragged, ss_plan_forward_ragged; 13: ss_ctc_beam_search / ss_ctc_beam_workspace_bytes; 14: ss_word_lm, ss_ctc_word_beam_search / ss_ctc_word_beam_workspace_bytes, ss_word_ngram_score; 15: ss_audio_resample_batch / ss_audio_resample_supported / ss_audio_resample_limits, ss_audio_level_batch; 16: ss_spectral_gate_profile / ss_spectral_gate_batch / ss_spectral_gate_limits; 17: ss_stft_logmel_fft_backward / ss_stft_logmel_fft_backward_workspace_bytes; 18: ss_ctc_align / ss_ctc_align_workspace_bytes).  Bindings must compare it with SS_ABI_VERSION at load time: a stale
+ * attention-image / LayerNorm-workspace entry points, ss_dtw_cumulative; 4: ss_loss_index_tables; 5: gate recomputation arguments of ss_bn_backward_sums / ss_bn_backward_apply; 7: ss_split_planes / ss_gemm_planes, ss_dw_job.flags, up to 24 jobs per grouped launch; 8: ss_stft_logmel_fft, the rejected-frame counter behind the matrix of ss_phoneme_confusion; 9: planes_hi / planes_lo / planes_only of ss_gemm_epilogue, dropout groups of the GEMM epilogue are row-major; 10: ss_emg_features_batch; 11: the ss_voc_* vocoder entry points; 12: the ragged-batch inference entry points ss_bn_apply_ragged, ss_relpos_attention_forward_ragged, ss_plan_forward_ragged; 13: ss_ctc_beam_search / ss_ctc_beam_workspace_bytes; 14: ss_word_lm, ss_ctc_word_beam_search / ss_ctc_word_beam_workspace_bytes, ss_word_ngram_score; 15: ss_audio_resample_batch / ss_audio_resample_supported / ss_audio_resample_limits, ss_audio_level_batch; 16: ss_spectral_gate_profile / ss_spectral_gate_batch / ss_spectral_gate_limits; 17: ss_stft_logmel_fft_backward / ss_stft_logmel_fft_backward_workspace_bytes; 18: ss_ctc_align / ss_ctc_align_workspace_bytes; 19: ss_spectral_gate_ns_batch).  Bindings must compare it with SS_ABI_VERSION at load time: a stale
  * library paired with newer headers would otherwise read garbage struct fields instead of failing. */
-#define SS_ABI_VERSION 18
+#define SS_ABI_VERSION 19
 int ss_abi_version(void);
 const char* ss_target_arch(void);
 
@@ -655,6 +655,20 @@ int ss_spectral_gate_profile(const float* x, const int64_t* table_dev, int frame
 int ss_spectral_gate_batch(const float* x, float* y, const int64_t* table_dev, int R, int64_t total_frames, const float* window_dev, const float* thresh,
                            int n_f, int n_t, double prop_decrease, uint32_t* bits_workspace, uint32_t* rowmax_workspace, float* frames_workspace,
                            uint32_t* bits_out, void* stream);
+/* Non-stationary spectral gating (csrc/spectral_gate_ns.hip, ABI 19): noisereduce 3's default mode, restated in f64 in tests/spectral_gate_ns_oracle.py --
+ * the threshold comes from the signal itself, no noise clip.  Framing, window_dev, table_dev, the limits of n_f / n_t and the overlap-add are those of
+ * ss_spectral_gate_batch.  A = |X|; per frequency row the level S = the one-pole smoother s[f] = b A[f] + (1 - b) s[f - 1] run forward from s[-1] := A[0]
+ * and then backward from S[F] := s[F - 1] (scipy.signal.filtfilt([b], [1, b - 1], A, padtype=None)), 0 < b <= 1
+ * (b = (sqrt(1 + 4 t^2) - 1) / (2 t^2), t = time constant in frames of 256 samples: data_utils.nonstationary_coefficient);
+ * r = (A - S) / S, 0 where S == 0 (digital silence gives a finite mask); m0 = 1 / (1 + exp(-(r - n_mult) slope)), slope > 0, the recurrences, r and the
+ * sigmoid in f64, m0 rounded to f32 once; mask = smooth(m0) prop_decrease + (1 - prop_decrease) with outer(tri(n_f), tri(n_t)) / its sum and zeros
+ * outside the 513 x F mask, f32 sums in ascending tap order (prop_decrease is applied AFTER the smoothing; in the stationary gate it comes before);
+ * y_f = irfft(X mask) W; out as in ss_spectral_gate_batch.  Four launches, no floating-point atomics: a batch gives bit for bit what single calls give.
+ * 1 <= R <= 65535.  Workspaces: mag_workspace and level_workspace total_frames x 513 floats each (A, replaced in place by m0; s between the two
+ * passes), frames_workspace total_frames x 1024 floats.  mask_out (NULL = off): total_frames x 513 floats, the UNSMOOTHED m0. */
+int ss_spectral_gate_ns_batch(const float* x, float* y, const int64_t* table_dev, int R, int64_t total_frames, const float* window_dev, double b,
+                              double n_mult, double slope, int n_f, int n_t, double prop_decrease, float* mag_workspace, float* level_workspace,
+                              float* frames_workspace, float* mask_out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The execution plan of the transduction model as native code: ONE call enqueues the whole forward pass of Model.forward

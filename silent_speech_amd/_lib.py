@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.environ.get('SS_AMD_LIBRARY') or os.path.join(_HERE, 'lib', 'libsilent_speech_hip.so')      # override: A/B runs of two builds on one box
 
 SS_F32, SS_BF16, SS_F64, SS_F32X3 = 0, 1, 2, 3
-ABI_VERSION = 18         # include/silent_speech_hip.h: SS_ABI_VERSION (struct layouts / signatures this binding was written against)
+ABI_VERSION = 19         # include/silent_speech_hip.h: SS_ABI_VERSION (struct layouts / signatures this binding was written against)
 OP_KC, OP_OC = 0, 1
 
 
@@ -124,6 +124,7 @@ SIGNATURES = {
     'ss_audio_level_batch': [_P, _P, _I, _L, _P, _L, _P, _P, _P],
     'ss_spectral_gate_profile': [_P, _P, _I, _P, ctypes.c_double, _P, _P, _P, _P],
     'ss_spectral_gate_batch': [_P, _P, _P, _I, _L, _P, _P, _I, _I, ctypes.c_double, _P, _P, _P, _P, _P],
+    'ss_spectral_gate_ns_batch': [_P, _P, _P, _I, _L, _P, ctypes.c_double, ctypes.c_double, ctypes.c_double, _I, _I, ctypes.c_double, _P, _P, _P, _P, _P],
     'ss_voc_conv1d': [_P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _I, _I, _F, _I, _F, _I, _P],
     'ss_voc_conv_transpose1d': [_P, _P, _P, _P, _I, _L, _I, _I, _I, _I, _I, _F, _I, _P],
     'ss_voc_tail': [_P, _P, _P, _P, _I, _L, _I, _I, _I, _F, _P],

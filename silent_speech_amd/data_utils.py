@@ -5,6 +5,8 @@
     resample_audio / resample_audio_batch / volume_gains: the band-limited resample (:75) and the levelling of a ragged batch (csrc/audio.hip)
     NoiseProfile / reduce_noise / reduce_noise_batch / clean_session: the stationary spectral gate and the levelling of data_collection/clean_audio.py
                                                                      (noisereduce's reduce_noise, csrc/spectral_gate.hip; file decoding stays out)
+    reduce_noise_nonstationary / reduce_noise_nonstationary_batch:    noisereduce's default, non-stationary gate for recordings without a silence clip
+                                                                     (csrc/spectral_gate_ns.hip; clean_session(gate='nonstationary'))
     get_emg_features(emg_data, debug=False)                                                            (:85-136)
     combine_fixed_length(tensor_list, length) / decollate_tensor(tensor, lengths)                      (:158-178)
     FeatureNormalizer                                                                                   (:138-156)
@@ -656,7 +658,8 @@ def reduce_noise(y, sr, y_noise=None, *, profile=None, stationary=True, prop_dec
     """noisereduce.reduce_noise(y=y, sr=sr, y_noise=y_noise, stationary=True, ...) (data_collection/clean_audio.py:53) on the device: a float32 tensor of
     len(y) samples.  The threshold comes from `profile`, else from y_noise, else from y itself."""
     if not stationary:
-        raise NotImplementedError('reduce_noise: the non-stationary gate is out of scope; only stationary=True is built')
+        raise NotImplementedError('reduce_noise: the non-stationary gate is out of scope; only stationary=True is built here -- '
+                                  'the non-stationary gate is reduce_noise_nonstationary')
     if not (float(sr) > 0):
         raise ValueError('the sample rate must be positive (got %r)' % (sr,))
     if np.ndim(y) != 1 or len(y) == 0:
@@ -666,6 +669,57 @@ def reduce_noise(y, sr, y_noise=None, *, profile=None, stationary=True, prop_dec
             raise ValueError('the noise clip must be 1-D and non-empty')
         profile = NoiseProfile.from_noise(y if y_noise is None else y_noise, sr, n_std_thresh_stationary)
     return reduce_noise_batch([y], profile, prop_decrease=prop_decrease, freq_mask_smooth_hz=freq_mask_smooth_hz, time_mask_smooth_ms=time_mask_smooth_ms)[0]
+
+
+def nonstationary_coefficient(sample_rate, time_constant_s=2.0):
+    """b of the non-stationary gate's one-pole level smoother, as noisereduce derives it: t = time_constant_s * sample_rate / 256 frames,
+    b = (sqrt(1 + 4 t^2) - 1) / (2 t^2)."""
+    if not (float(sample_rate) > 0):
+        raise ValueError('the sample rate must be positive (got %r)' % (sample_rate,))
+    if not (float(time_constant_s) > 0):
+        raise ValueError('time_constant_s must be positive (got %r)' % (time_constant_s,))
+    t = float(time_constant_s) * float(sample_rate) / GATE_HOP
+    return (np.sqrt(1.0 + 4.0 * t * t) - 1.0) / (2.0 * t * t)
+
+
+def _gate_ns_rows(flat, out, lens, rows, b, n_f, n_t, n_mult=2.0, slope=10.0, prop_decrease=1.0, return_mask=False):
+    """One ss_spectral_gate_ns_batch launch sequence: the signals `rows` of the flat buffer `flat` -> their places in `out`."""
+    from . import torch_ops  # noqa: F401
+    table, total_frames = _gate_table(lens, flat.device, rows)
+    return torch.ops.silent_speech.spectral_gate_nonstationary(flat, out, table, _gate_windows(flat.device), total_frames, float(b), float(n_mult), float(slope),
+                                                               n_f, n_t, float(prop_decrease), bool(return_mask))
+
+
+def reduce_noise_nonstationary_batch(signals, sample_rate, *, time_constant_s=2.0, thresh_n_mult_nonstationary=2.0, sigmoid_slope_nonstationary=10.0,
+                                     prop_decrease=1.0, freq_mask_smooth_hz=500, time_mask_smooth_ms=50, return_mask=False):
+    """noisereduce.reduce_noise(y, sr) -- its default, NON-STATIONARY gate -- of every signal of a batch, one launch per kernel for the whole batch
+    (csrc/spectral_gate_ns.hip).  No noise clip: per frequency row the level is the signal's own |STFT| smoothed forward and backward over time with the
+    time constant time_constant_s, and the mask a sigmoid on the relative excess over it.  Every signal is ONE chunk with scipy's steady-state initial
+    conditions (noisereduce cuts at 600 000 samples and surrounds each chunk with zeros: DESIGN section 8).  signals: a list of 1-D signals, or
+    (flat f32 tensor, lengths).  Returns (flat f32 device tensor, lengths) -- and the unsmoothed mask (total frames, 513) f32 as a third item with
+    return_mask."""
+    b = nonstationary_coefficient(sample_rate, time_constant_s)
+    if not (float(sigmoid_slope_nonstationary) > 0):
+        raise ValueError('sigmoid_slope_nonstationary must be positive (got %r)' % (sigmoid_slope_nonstationary,))
+    if not np.isfinite(float(thresh_n_mult_nonstationary)):
+        raise ValueError('thresh_n_mult_nonstationary must be finite')
+    if not (0.0 <= float(prop_decrease) <= 1.0):
+        raise ValueError('prop_decrease must lie in [0, 1]')
+    n_f, n_t = gate_smoothing(sample_rate, freq_mask_smooth_hz, time_mask_smooth_ms)
+    flat, lens = _flat_signals(signals)
+    out = torch.empty_like(flat)
+    mask = _gate_ns_rows(flat, out, lens, None, b, n_f, n_t, thresh_n_mult_nonstationary, sigmoid_slope_nonstationary, prop_decrease, return_mask)
+    return (out, lens, mask) if return_mask else (out, lens)
+
+
+def reduce_noise_nonstationary(y, sr, *, time_constant_s=2.0, thresh_n_mult_nonstationary=2.0, sigmoid_slope_nonstationary=10.0, prop_decrease=1.0,
+                               freq_mask_smooth_hz=500, time_mask_smooth_ms=50):
+    """noisereduce.reduce_noise(y=y, sr=sr) with its default stationary=False on the device: a float32 tensor of len(y) samples."""
+    if np.ndim(y) != 1 or len(y) == 0:
+        raise ValueError('y must be 1-D and non-empty')
+    return reduce_noise_nonstationary_batch([y], sr, time_constant_s=time_constant_s, thresh_n_mult_nonstationary=thresh_n_mult_nonstationary,
+                                            sigmoid_slope_nonstationary=sigmoid_slope_nonstationary, prop_decrease=prop_decrease,
+                                            freq_mask_smooth_hz=freq_mask_smooth_hz, time_mask_smooth_ms=time_mask_smooth_ms)[0]
 
 
 def session_gains(max_rmses, silent_cutoff=0.02, smoothing_width=20, target_rms=0.2):
@@ -681,18 +735,27 @@ def session_gains(max_rmses, silent_cutoff=0.02, smoothing_width=20, target_rms=
     return gains
 
 
-def clean_session(signals, sample_rate, noise=None):
+def clean_session(signals, sample_rate, noise=None, *, gate='stationary'):
     """data_collection/clean_audio.py clean_directory from decoded arrays: the session's recordings in file order (signals[0] is the silence clip
     0_audio unless `noise` is given) -> (flat f32 device tensor at 22 050 Hz, lengths).  Max frame RMS per file (volume_levels on the raw signals) ->
     the +-20-file smoothing on the host -> the stationary gate against the noise clip's profile -> the band-limited resample to 22 050 Hz with the
-    gain 0.2 / smoothed max -> x / max |x| * 0.99 where the peak exceeds 0.99.  A long run of quiet audio skips the levelling, as the reference does."""
+    gain 0.2 / smoothed max -> x / max |x| * 0.99 where the peak exceeds 0.99.  A long run of quiet audio skips the levelling, as the reference does.
+    gate='nonstationary': for sessions without a silence clip -- no profile is made, every signal (signals[0] included) goes through
+    reduce_noise_nonstationary_batch with its defaults, gated against itself; `noise` must then be None."""
+    if gate not in ('stationary', 'nonstationary'):
+        raise ValueError("gate: 'stationary' or 'nonstationary' (got %r)" % (gate,))
+    if gate == 'nonstationary' and noise is not None:
+        raise ValueError("gate='nonstationary' takes no noise clip")
     flat, lens = _flat_signals(signals)
     levels = volume_levels((flat, lens))[0][:, 0].cpu().tolist()
     gains = session_gains(levels)
-    if noise is None:
-        noise = flat[:lens[0]]
-    profile = NoiseProfile.from_noise(noise, sample_rate)
-    clean, lens = reduce_noise_batch((flat, lens), profile)
+    if gate == 'nonstationary':
+        clean, lens = reduce_noise_nonstationary_batch((flat, lens), sample_rate)
+    else:
+        if noise is None:
+            noise = flat[:lens[0]]
+        profile = NoiseProfile.from_noise(noise, sample_rate)
+        clean, lens = reduce_noise_batch((flat, lens), profile)
     out, out_lens = resample_audio_batch((clean, lens), sample_rate, 22050, gains=gains)
     if gains is not None:
         peak = volume_levels((out, out_lens))[0][:, 1]

@@ -170,6 +170,18 @@ def _feature_frames(n_1k):
     return 0 if n516 < 16 else 1 + (n516 - 16) // 6
 
 
+def _noise_gate(rec):
+    """True where the recording asks for the non-stationary gate (noise_gate='nonstationary'); a noise_profile next to it is refused."""
+    mode = rec.get('noise_gate')
+    if mode is None:
+        return False
+    if mode != 'nonstationary':
+        raise ValueError("noise_gate: 'nonstationary' or None (got %r); the stationary gate is asked for with a noise_profile" % (mode,))
+    if rec.get('noise_profile') is not None:
+        raise ValueError("a recording carries either a noise_profile (stationary gate) or noise_gate='nonstationary', not both")
+    return True
+
+
 class DeviceBatchBuilder(object):
     """`[dataset[i] for i in batch]` + `collate_raw` (read_emg.py:223-296) on the MI355X, from in-memory recordings: what
     load_utterance / load_audio / EMGDataset.__getitem__ compute per utterance on the host (and memoise with lru_cache) is computed
@@ -183,6 +195,9 @@ class DeviceBatchBuilder(object):
         audio_rate int              optional, default 22 050: the rate `audio` is stored at (the corpus: 16 000); the twin carries its own
         noise_profile               optional data_utils.NoiseProfile (of the session's silence clip, at the stored rate): the audio goes through the
                                     stationary spectral gate (data_collection/clean_audio.py:53) before anything else; the twin carries its own
+        noise_gate                  optional, 'nonstationary': for recordings without a silence clip -- the audio goes through noisereduce's default,
+                                    non-stationary gate at the stored rate instead (data_utils.reduce_noise_nonstationary with its defaults); a
+                                    recording with both keys is refused
         phonemes (frames,) int64    read_phonemes output (optional: 'sil' everywhere like read_emg.py:98)
         silent bool, text_int int64, session_index int
         parallel                    for silent recordings: the voiced twin (same dict shape); its audio features and phonemes become
@@ -192,7 +207,8 @@ class DeviceBatchBuilder(object):
                 (chunk, channel) pairs over all recordings) -> crop -> np.interp to 689.06 Hz -> rows 8..8+8n (:90) gathered by one
                 launch -> /20, 50 tanh(./50) (:227-228) in one kernel
         audio : recordings with a noise_profile: noisereduce's stationary gate at the stored rate, one launch sequence per distinct profile over the
-                uploaded batch (csrc/spectral_gate.hip); recordings without one are passed on as they are ->
+                uploaded batch (csrc/spectral_gate.hip); recordings with noise_gate='nonstationary': one launch sequence per distinct stored rate
+                (csrc/spectral_gate_ns.hip); recordings with neither are passed on as they are ->
                 recordings at another rate than 22 050 Hz: scipy.signal.resample_poly to 22 050 Hz (data_utils.py:75), one launch per distinct rate over
                 the uploaded batch, results in batch order (csrc/audio.hip); every frame count follows the resampled length ceil(L up / down) ->
                 clip + reflect pad (ragged) -> one hop-strided DFT GEMM -> |.| -> one mel GEMM + log clamp -> FeatureNormalizer, all
@@ -274,11 +290,13 @@ class DeviceBatchBuilder(object):
     @staticmethod
     def _gated(sig, recs):
         """The batch's audio with the recordings that carry a noise_profile replaced by their gated signals (reduce_noise with its defaults at the
-        recording's stored rate), in the same order and layout: one launch sequence per distinct profile."""
-        from .data_utils import _flat_signals, _gate_rows, gate_smoothing
+        recording's stored rate), in the same order and layout: one launch sequence per distinct profile; and those that carry
+        noise_gate='nonstationary' by their self-gated signals: one launch sequence per distinct stored rate."""
+        from .data_utils import _flat_signals, _gate_ns_rows, _gate_rows, gate_smoothing, nonstationary_coefficient
         flat, lens = _flat_signals(sig)
         profiles = [r.get('noise_profile') for r in recs]
-        out = torch.empty_like(flat) if all(p is not None for p in profiles) else flat.clone()
+        self_gated = [_noise_gate(r) for r in recs]
+        out = torch.empty_like(flat) if all(p is not None or g for p, g in zip(profiles, self_gated)) else flat.clone()
         done = set()
         for p in profiles:
             if p is None or id(p) in done:
@@ -286,6 +304,11 @@ class DeviceBatchBuilder(object):
             done.add(id(p))
             n_f, n_t = gate_smoothing(p.sr)
             _gate_rows(flat, out, lens, [u for u, q in enumerate(profiles) if q is p], p, n_f, n_t)
+        # noise_gate='nonstationary': the recordings that share a stored rate (it fixes b and the smoothing widths) in one launch sequence
+        rates = [int(r.get('audio_rate', 22050)) for r in recs]
+        for rate in sorted(set(rt for rt, g in zip(rates, self_gated) if g)):
+            n_f, n_t = gate_smoothing(rate)
+            _gate_ns_rows(flat, out, lens, [u for u, g in enumerate(self_gated) if g and rates[u] == rate], nonstationary_coefficient(rate), n_f, n_t)
         return out, lens
 
     def _frames(self, rec, mel_frames, limit):
@@ -298,6 +321,7 @@ class DeviceBatchBuilder(object):
         # audio of every recording whose mel frames are needed: own audio (lengths; targets when voiced) and the voiced twins
         twins = [r['parallel'] if r['silent'] else None for r in recordings]
         audio_src = list(recordings) + [t for t in twins if t is not None]
+        self_gated = [_noise_gate(r) for r in audio_src]                                   # (refuses a recording with both gate keys before any work)
         # with emg_features: the twins whose features are computed here ride along in the EMG chain (after the own recordings)
         feat_twins = [i for i, t in enumerate(twins) if self.emg_features and t is not None and t.get('emg_features') is None]
         emg_src = list(recordings) + [twins[i] for i in feat_twins]
@@ -330,7 +354,7 @@ class DeviceBatchBuilder(object):
                     side.wait_stream(main)                                                  # device tensors handed in: produced on the caller's stream
                     for t in sig:
                         t.record_stream(side)
-            if any(r.get('noise_profile') is not None for r in audio_src):
+            if any(self_gated) or any(r.get('noise_profile') is not None for r in audio_src):
                 sig = self._gated(sig, audio_src)
             if any(int(r.get('audio_rate', 22050)) != 22050 for r in audio_src):
                 sig = self._to_22050(sig, [int(r.get('audio_rate', 22050)) for r in audio_src])

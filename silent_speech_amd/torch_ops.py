@@ -14,6 +14,7 @@
     emg_features                     data_utils.py:85-136 (get_emg_features; no autograd: the reference's features are numpy)
     audio_resample / audio_level     the band-limited resample (:75) and normalize_volume's levels (:19-27) of load_audio for a ragged batch of stored audio
     spectral_gate_profile / spectral_gate      the stationary noise gate of data_collection/clean_audio.py:53 (noisereduce's reduce_noise) for a ragged batch
+    spectral_gate_nonstationary      noisereduce's default, non-stationary gate (no noise clip: the level follows the recording itself) for a ragged batch
     fused_adamw                      torch.optim.AdamW over the flat parameter arena (transduction_model.py:178,210)
     vocoder_conv1d / vocoder_conv_transpose1d / vocoder_tail      the three kernel families of the HiFi-GAN generator (vocoder.py:16-36), inference only
 
@@ -670,6 +671,45 @@ def _(flat, out, table, windows, thresh, total_frames, n_f, n_t, prop_decrease, 
     return flat.new_empty((total_frames if return_bits else 0, GATE_ROW_DWORDS), dtype=torch.int32)
 
 
+@torch.library.custom_op('silent_speech::spectral_gate_nonstationary', mutates_args=('out',))
+def spectral_gate_nonstationary(flat: Tensor, out: Tensor, table: Tensor, windows: Tensor, total_frames: int, b: float, n_mult: float, slope: float, n_f: int,
+                                n_t: int, prop_decrease: float, return_mask: bool) -> Tensor:
+    """noisereduce's non-stationary gate over every signal of a ragged batch (ss_spectral_gate_ns_batch in include/silent_speech_hip.h): no noise clip, the
+    level per frequency row is the signal's own magnitude smoothed forward and backward over time with the coefficient b
+    (data_utils.nonstationary_coefficient), the mask a sigmoid of slope `slope` on the relative excess over n_mult.  flat, table, windows, n_f, n_t as for
+    spectral_gate.  Writes the gated signals into `out` (flat's layout and size; nothing else of it is touched) and returns the UNSMOOTHED mask m0
+    (total_frames, 513) f32 when return_mask, else an empty (0, 513) tensor."""
+    name = 'spectral_gate_nonstationary'
+    _gate_check(name, flat, table, windows)
+    dev = flat.device
+    if not (0.0 < b <= 1.0):
+        raise ValueError('%s: the smoothing coefficient b must lie in (0, 1]' % name)
+    if not (slope > 0.0) or n_mult != n_mult:
+        raise ValueError('%s: the sigmoid slope must be positive' % name)
+    if not (0 <= n_f <= GATE_MAX_NF and 0 <= n_t <= GATE_MAX_NT):
+        raise ValueError('%s: mask smoothing over %d rows x %d frames is not supported (at most %d x %d)' % (name, n_f, n_t, GATE_MAX_NF, GATE_MAX_NT))
+    if not (0.0 <= prop_decrease <= 1.0):
+        raise ValueError('%s: prop_decrease must lie in [0, 1]' % name)
+    R = table.shape[0]
+    if total_frames < 2 * R:
+        raise ValueError('%s: every signal needs at least one sample' % name)
+    if out.shape != flat.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise RuntimeError('%s: out must be a contiguous float32 buffer of the size and on the device of the input' % name)
+    mag = torch.empty((total_frames, GATE_BINS), dtype=torch.float32, device=dev)
+    level = torch.empty((total_frames, GATE_BINS), dtype=torch.float32, device=dev)
+    frames = torch.empty((total_frames, 1024), dtype=torch.float32, device=dev)
+    mask = torch.empty((total_frames if return_mask else 0, GATE_BINS), dtype=torch.float32, device=dev)
+    _lib.check(_L().ss_spectral_gate_ns_batch(_p(flat), _p(out), _p(table), R, total_frames, _p(windows), float(b), float(n_mult), float(slope), n_f, n_t,
+                                              float(prop_decrease), _p(mag), _p(level), _p(frames), _p(mask) if return_mask else None, _lib.stream_of(flat)),
+               'ss_spectral_gate_ns_batch')
+    return mask
+
+
+@spectral_gate_nonstationary.register_fake
+def _(flat, out, table, windows, total_frames, b, n_mult, slope, n_f, n_t, prop_decrease, return_mask):
+    return flat.new_empty((total_frames if return_mask else 0, GATE_BINS))
+
+
 # ------------------------------------------------------------------------------------------------ fused_adamw
 @torch.library.custom_op('silent_speech::fused_adamw', mutates_args=('p', 'm', 'v'))
 def fused_adamw(p: Tensor, g: Tensor, m: Tensor, v: Tensor, n: int, lr: float, step: int, beta1: float, beta2: float, eps: float,
@@ -740,5 +780,5 @@ def _(x, w, k, slope):
 
 
 OPS = ('model_forward', 'model_forward_ragged', 'model_backward', 'dtw_loss', 'dtw_align', 'ctc_loss', 'ctc_beam_search', 'ctc_word_beam_search', 'ctc_forced_align', 'word_ngram_score', 'stft_logmel', 'stft_logmel_backward', 'stft_logmel_ragged', 'stft_logmel_ragged_backward',
-       'emg_features', 'audio_resample', 'audio_level', 'spectral_gate_profile', 'spectral_gate', 'fused_adamw',
+       'emg_features', 'audio_resample', 'audio_level', 'spectral_gate_profile', 'spectral_gate', 'spectral_gate_nonstationary', 'fused_adamw',
        'vocoder_conv1d', 'vocoder_conv_transpose1d', 'vocoder_tail')
