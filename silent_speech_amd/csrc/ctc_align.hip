@@ -18,9 +18,8 @@
 //            ascending order.
 //   rows     of no utterance get -2 from additional workgroups of the same launch (a row asks every table entry: rows * n_utt / 64 wave steps).
 // Every loop is bounded by T, S or n_utt; there is no inter-workgroup communication and no spinning.
-#include "common.h"
+#include "ctc_beam_common.h"   // ctc_utt_frames / ctc_utt_locate: the clamped walk of the utterance table
 #include "silent_speech_hip.h"
-#include <math.h>
 
 namespace {
 constexpr int AL_FB = 16, AL_BT = 64, AL_MAX_S = 511, AL_MAX_V = 4096, AL_MAX_KT = 8, AL_FILL_ROWS = 512;
@@ -37,18 +36,6 @@ __device__ __forceinline__ void al_fence() {
     __threadfence();
 #endif
     __syncthreads();
-}
-
-// Frames of table entry j and its first frame, clamped the way ss_ctc_beam_search clamps them: `off` (the frames of the entries before it) is advanced, the
-// result stays inside the workspace (total_frames) and inside [0, rows).
-__device__ __forceinline__ int al_frames(const AlArgs& a, int j, long long& off, long long& f0) {
-    f0 = a.utt[4 * j];
-    long long n = a.utt[4 * j + 1];
-    if (n < 0) n = 0;
-    if (n > a.total_frames - off) n = a.total_frames - off;
-    off += n;
-    if (f0 < 0 || f0 > a.rows || n > a.rows - f0) n = 0;
-    return (int)n;
 }
 
 template <int KT, bool CTC>
@@ -226,16 +213,14 @@ __global__ __launch_bounds__(64) void ctc_align_kernel(const AlArgs a)
         for (long long r = fb * 64 + lane; r < a.rows; r += nfill * 64) {
             bool covered = false;
             long long off = 0, f0;
-            for (int j = 0; j < a.n_utt; ++j) { const int n = al_frames(a, j, off, f0); covered |= r >= f0 && r - f0 < n; }
+            for (int j = 0; j < a.n_utt; ++j) { const int n = ctc_utt_frames(a.utt, 4, j, a.total_frames, a.rows, off, f0); covered |= r >= f0 && r - f0 < n; }
             if (!covered) a.frame_token[r] = -2;
         }
         return;
     }
     const int u = blockIdx.x;
-    long long off = 0, f0 = 0;
-    for (int j = 0; j < u; ++j) al_frames(a, j, off, f0);
-    const long long off_u = off;
-    const int T = al_frames(a, u, off, f0);
+    long long off_u, f0;
+    const int T = ctc_utt_locate(a.utt, 4, u, a.total_frames, a.rows, off_u, f0);
     const long long tg0 = a.utt[4 * u + 2], Sl = a.utt[4 * u + 3];
     const bool table_ok = tg0 >= 0 && Sl >= 0 && Sl <= a.max_s && tg0 <= a.n_targets - Sl;
     const int S = table_ok ? (int)Sl : 0;

@@ -247,33 +247,31 @@ ctc_loss.register_autograd(_ctc_bwd, setup_context=_ctc_setup)
 
 
 # ------------------------------------------------------------------------------------------------ ctc_beam_search (inference only: no autograd)
-@torch.library.custom_op('silent_speech::ctc_beam_search', mutates_args=())
-def ctc_beam_search(logits: Tensor, utt: Tensor, V: int, blank: int, total_frames: int, max_len: int, beam_width: int, n_best: int,
-                    lm: Optional[Tensor], alpha: float, beta: float) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
-    """CTC prefix beam search (ss_ctc_beam_search in include/silent_speech_hip.h states the algorithm).  logits [M][ld >= V] f32 raw model
-    outputs; utt [n][2] int64 on the device = (first frame, frames) per utterance, packed or slot layout; total_frames >= the sum of the
-    frames, max_len >= the longest utterance; lm: optional (V, V, V - 1) f32 table of natural-log label probabilities, weights alpha, beta.
-    Returns (labels [n][n_best][max_len] int32 with -1 behind the end, lengths [n][n_best] int32 (-1: no such rank), scores, CTC scores [n][n_best])."""
-    dev = logits.device
+def _beam_search_checks(name, min_classes, logits, utt, V, blank, total_frames, max_len, beam_width, n_best):
+    """The argument checks ctc_beam_search and ctc_word_beam_search share."""
     if logits.dim() != 2 or logits.dtype != torch.float32 or not logits.is_contiguous():
-        raise RuntimeError('ctc_beam_search: logits must be a contiguous (frames, ld) float32 matrix')
-    if utt.dim() != 2 or utt.shape[1] != 2 or utt.dtype != torch.int64 or not utt.is_contiguous() or utt.device != dev:
-        raise RuntimeError('ctc_beam_search: utt must be a contiguous (n, 2) int64 table on the device of the logits')
-    if lm is not None and (lm.shape != (V, V, V - 1) or lm.dtype != torch.float32 or not lm.is_contiguous() or lm.device != dev):
-        raise RuntimeError('ctc_beam_search: the label table must be a contiguous (%d, %d, %d) float32 tensor on the device of the logits' % (V, V, V - 1))
-    # everything the launches below rely on is checked HERE: ss_frame_lse reads V columns at stride ld whatever it is told
-    if not (1 <= V <= min(logits.shape[1], 128)) or not (0 <= blank < V):
-        raise RuntimeError('ctc_beam_search: %d classes (1 .. min(row stride %d, 128)), blank %d' % (V, logits.shape[1], blank))
+        raise RuntimeError('%s: logits must be a contiguous (frames, ld) float32 matrix' % name)
+    if utt.dim() != 2 or utt.shape[1] != 2 or utt.dtype != torch.int64 or not utt.is_contiguous() or utt.device != logits.device:
+        raise RuntimeError('%s: utt must be a contiguous (n, 2) int64 table on the device of the logits' % name)
+    # everything the launches rely on is checked HERE: ss_frame_lse reads V columns at stride ld whatever it is told
+    if not (min_classes <= V <= min(logits.shape[1], 128)) or not (0 <= blank < V):
+        raise RuntimeError('%s: %d classes (%d .. min(row stride %d, 128)), blank %d' % (name, V, min_classes, logits.shape[1], blank))
     if not (1 <= beam_width <= 128) or not (1 <= n_best <= beam_width):
-        raise RuntimeError('ctc_beam_search: beam width %d (1 .. 128), n_best %d (1 .. beam width)' % (beam_width, n_best))
+        raise RuntimeError('%s: beam width %d (1 .. 128), n_best %d (1 .. beam width)' % (name, beam_width, n_best))
     if max_len < 1 or total_frames < 0:
-        raise RuntimeError('ctc_beam_search: max_len %d, total_frames %d' % (max_len, total_frames))
+        raise RuntimeError('%s: max_len %d, total_frames %d' % (name, max_len, total_frames))
+
+
+def _beam_search_buffers(name, logits, utt, V, total_frames, max_len, beam_width, n_best, workspace_bytes):
+    """Behind the checks: the per-frame lse launch, the trie workspace and the outputs every search has.
+    Returns (lse, workspace, stream, (labels, lengths, scores, ctc_scores))."""
+    dev = logits.device
     M, ld = logits.shape
     n = utt.shape[0]
     st = _lib.stream_of(logits)
-    ws_bytes = _L().ss_ctc_beam_workspace_bytes(n, total_frames, beam_width)
+    ws_bytes = workspace_bytes(n, total_frames, beam_width)
     if ws_bytes < 0:
-        raise RuntimeError('ctc_beam_search: beam width %d (1 .. 128)' % beam_width)
+        raise RuntimeError('%s: beam width %d (1 .. 128)' % (name, beam_width))
     lse = torch.empty(max(M, 1), dtype=torch.float32, device=dev)
     amax = torch.empty(max(M, 1), dtype=torch.int32, device=dev)
     if M:
@@ -283,9 +281,24 @@ def ctc_beam_search(logits: Tensor, utt: Tensor, V: int, blank: int, total_frame
     lengths = torch.empty((n, n_best), dtype=torch.int32, device=dev)
     scores = torch.empty((n, n_best), dtype=torch.float32, device=dev)
     ctc_scores = torch.empty((n, n_best), dtype=torch.float32, device=dev)
-    _lib.check(_L().ss_ctc_beam_search(_p(logits), ld, V, blank, M, _p(lse), _p(utt) if n else None, n, total_frames, beam_width, n_best,
-                                       _p(lm), alpha, beta, _p(ws), max_len, _p(labels), _p(lengths), _p(scores), _p(ctc_scores), st), 'ss_ctc_beam_search')
-    return labels, lengths, scores, ctc_scores
+    return lse, ws, st, (labels, lengths, scores, ctc_scores)
+
+
+@torch.library.custom_op('silent_speech::ctc_beam_search', mutates_args=())
+def ctc_beam_search(logits: Tensor, utt: Tensor, V: int, blank: int, total_frames: int, max_len: int, beam_width: int, n_best: int,
+                    lm: Optional[Tensor], alpha: float, beta: float) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """CTC prefix beam search (ss_ctc_beam_search in include/silent_speech_hip.h states the algorithm).  logits [M][ld >= V] f32 raw model
+    outputs; utt [n][2] int64 on the device = (first frame, frames) per utterance, packed or slot layout; total_frames >= the sum of the
+    frames, max_len >= the longest utterance; lm: optional (V, V, V - 1) f32 table of natural-log label probabilities, weights alpha, beta.
+    Returns (labels [n][n_best][max_len] int32 with -1 behind the end, lengths [n][n_best] int32 (-1: no such rank), scores, CTC scores [n][n_best])."""
+    _beam_search_checks('ctc_beam_search', 1, logits, utt, V, blank, total_frames, max_len, beam_width, n_best)
+    if lm is not None and (lm.shape != (V, V, V - 1) or lm.dtype != torch.float32 or not lm.is_contiguous() or lm.device != logits.device):
+        raise RuntimeError('ctc_beam_search: the label table must be a contiguous (%d, %d, %d) float32 tensor on the device of the logits' % (V, V, V - 1))
+    lse, ws, st, out = _beam_search_buffers('ctc_beam_search', logits, utt, V, total_frames, max_len, beam_width, n_best, _L().ss_ctc_beam_workspace_bytes)
+    n = utt.shape[0]
+    _lib.check(_L().ss_ctc_beam_search(_p(logits), logits.shape[1], V, blank, logits.shape[0], _p(lse), _p(utt) if n else None, n, total_frames, beam_width, n_best,
+                                       _p(lm), alpha, beta, _p(ws), max_len, *(_p(t) for t in out), st), 'ss_ctc_beam_search')
+    return out
 
 
 @ctc_beam_search.register_fake
@@ -331,18 +344,9 @@ def ctc_word_beam_search(logits: Tensor, utt: Tensor, V: int, blank: int, space:
     id of the start context and the longest probe sequence of each hash table.
     Returns (labels, lengths, scores, CTC scores) as ctc_beam_search and complete [n][n_best] int32 (1 / 0; -1: no such rank)."""
     dev = logits.device
-    if logits.dim() != 2 or logits.dtype != torch.float32 or not logits.is_contiguous():
-        raise RuntimeError('ctc_word_beam_search: logits must be a contiguous (frames, ld) float32 matrix')
-    if utt.dim() != 2 or utt.shape[1] != 2 or utt.dtype != torch.int64 or not utt.is_contiguous() or utt.device != dev:
-        raise RuntimeError('ctc_word_beam_search: utt must be a contiguous (n, 2) int64 table on the device of the logits')
-    if not (2 <= V <= min(logits.shape[1], 128)) or not (0 <= blank < V):
-        raise RuntimeError('ctc_word_beam_search: %d classes (2 .. min(row stride %d, 128)), blank %d' % (V, logits.shape[1], blank))
+    _beam_search_checks('ctc_word_beam_search', 2, logits, utt, V, blank, total_frames, max_len, beam_width, n_best)
     if not (0 <= space < V) or space == blank:
         raise RuntimeError('ctc_word_beam_search: space class %d (0 .. %d, not the blank %d)' % (space, V - 1, blank))
-    if not (1 <= beam_width <= 128) or not (1 <= n_best <= beam_width):
-        raise RuntimeError('ctc_word_beam_search: beam width %d (1 .. 128), n_best %d (1 .. beam width)' % (beam_width, n_best))
-    if max_len < 1 or total_frames < 0:
-        raise RuntimeError('ctc_word_beam_search: max_len %d, total_frames %d' % (max_len, total_frames))
     if lex_child.dim() != 2 or lex_child.shape[0] < 1 or lex_child.shape[1] != V - 1 or lex_child.dtype != torch.int32 or not lex_child.is_contiguous() or \
             lex_child.device != dev or tuple(lex_word.shape) != (lex_child.shape[0],) or lex_word.dtype != torch.int32 or not lex_word.is_contiguous() or lex_word.device != dev:
         raise RuntimeError('ctc_word_beam_search: the lexicon must be contiguous int32 tensors (n_nodes >= 1, %d) and (n_nodes) on the device of the logits' % (V - 1))
@@ -350,26 +354,12 @@ def ctc_word_beam_search(logits: Tensor, utt: Tensor, V: int, blank: int, space:
     if not (0 <= n_vocab <= lm.n_uni) or not (0 <= start < lm.n_uni):
         raise RuntimeError('ctc_word_beam_search: %d words, start id %d, but %d word ids' % (n_vocab, start, lm.n_uni))
     lm.lex_child, lm.lex_word, lm.n_nodes, lm.n_vocab, lm.start = lex_child.data_ptr(), lex_word.data_ptr(), lex_child.shape[0], n_vocab, start
-    M, ld = logits.shape
+    lse, ws, st, out = _beam_search_buffers('ctc_word_beam_search', logits, utt, V, total_frames, max_len, beam_width, n_best, _L().ss_ctc_word_beam_workspace_bytes)
     n = utt.shape[0]
-    st = _lib.stream_of(logits)
-    ws_bytes = _L().ss_ctc_word_beam_workspace_bytes(n, total_frames, beam_width)
-    if ws_bytes < 0:
-        raise RuntimeError('ctc_word_beam_search: beam width %d (1 .. 128)' % beam_width)
-    lse = torch.empty(max(M, 1), dtype=torch.float32, device=dev)
-    amax = torch.empty(max(M, 1), dtype=torch.int32, device=dev)
-    if M:
-        _lib.check(_L().ss_frame_lse(_p(logits), ld, 0, V, M, _p(lse), _p(amax), st), 'ss_frame_lse')
-    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
-    labels = torch.empty((n, n_best, max_len), dtype=torch.int32, device=dev)
-    lengths = torch.empty((n, n_best), dtype=torch.int32, device=dev)
-    scores = torch.empty((n, n_best), dtype=torch.float32, device=dev)
-    ctc_scores = torch.empty((n, n_best), dtype=torch.float32, device=dev)
     complete = torch.empty((n, n_best), dtype=torch.int32, device=dev)
-    _lib.check(_L().ss_ctc_word_beam_search(_p(logits), ld, V, blank, space, M, _p(lse), _p(utt) if n else None, n, total_frames, beam_width, n_best,
-                                            ctypes.byref(lm), alpha, beta, _p(ws), max_len, _p(labels), _p(lengths), _p(scores), _p(ctc_scores),
-                                            _p(complete), st), 'ss_ctc_word_beam_search')
-    return labels, lengths, scores, ctc_scores, complete
+    _lib.check(_L().ss_ctc_word_beam_search(_p(logits), logits.shape[1], V, blank, space, logits.shape[0], _p(lse), _p(utt) if n else None, n, total_frames, beam_width,
+                                            n_best, ctypes.byref(lm), alpha, beta, _p(ws), max_len, *(_p(t) for t in out), _p(complete), st), 'ss_ctc_word_beam_search')
+    return out + (complete,)
 
 
 @ctc_word_beam_search.register_fake

@@ -19,45 +19,18 @@ from silent_speech_amd import torch_ops
 from silent_speech_amd.architecture import Model
 from tests import ctc_beam_oracle as oracle
 from tests.backend import dev, is_emu  # noqa: F401
+from tests.ctc_beam_helpers import from_probs as _from_probs, layout as _layout, noise as _noise, same as _same, strings as _strings
 
 EXACT_BAR = 2e-5
 
 
-def _search(dev, utts, blank, W, n_best, lm=None, alpha=0.0, beta=0.0, layout='packed', ld=None, gaps=None):
-    """utts: list of (T_i, V) float32 arrays.  layout 'packed': back to back, or with gaps[i] NaN rows in front of utterance i; 'slots': slot b
-    starts at b * T_max, NaN filler.  ld > V: NaN in the extra columns.  Returns numpy (labels, lengths, scores, ctc scores)."""
-    V = utts[0].shape[1]
-    ld = ld or V
-    frames = [int(x.shape[0]) for x in utts]
-    if layout == 'slots':
-        first = [b * max(frames) for b in range(len(utts))]
-        rows = len(utts) * max(frames)
-    else:
-        gaps = gaps or [0] * len(utts)
-        first, at = [], 0
-        for g, n in zip(gaps, frames):
-            first.append(at + g)
-            at += g + n
-        rows = at
-    flat = np.full((rows, ld), np.nan, dtype=np.float32)
-    for f0, x in zip(first, utts):
-        flat[f0:f0 + x.shape[0], :V] = x
-    utt = torch.tensor([[f, n] for f, n in zip(first, frames)], dtype=torch.int64).reshape(len(utts), 2).to(dev)
+def _search(dev, utts, blank, W, n_best, lm=None, alpha=0.0, beta=0.0, **how):
+    """utts: list of (T_i, V) float32 arrays, laid out by ctc_beam_helpers.layout(**how).  Returns numpy (labels, lengths, scores, ctc scores)."""
+    flat, utt, V, total, longest = _layout(dev, utts, **how)
     if lm is not None:
         lm = torch.as_tensor(lm, dtype=torch.float32).to(dev)
-    out = torch.ops.silent_speech.ctc_beam_search(torch.from_numpy(flat).to(dev), utt, V, blank, sum(frames), max(max(frames), 1), W, n_best, lm, alpha, beta)
+    out = torch.ops.silent_speech.ctc_beam_search(flat, utt, V, blank, total, longest, W, n_best, lm, alpha, beta)
     return tuple(t.cpu().numpy() for t in out)
-
-
-def _strings(out, b):
-    labels, lengths = out[0], out[1]
-    return [tuple(labels[b, r, :lengths[b, r]].tolist()) for r in range(lengths.shape[1]) if lengths[b, r] >= 0]
-
-
-def _noise(rng, T, V, blank, s):
-    x = rng.standard_normal((T, V)) * s
-    x[:, blank] += s
-    return x.astype(np.float32)
 
 
 # ---------------------------------------------------------------------------------------------- 0. the oracle itself
@@ -118,10 +91,6 @@ def test_exact_regime_short_utterances_mark_missing_ranks(dev, T):
 
 
 # ---------------------------------------------------------------------------------------------- 2. the rules best-path decoding gets wrong
-def _from_probs(rows):
-    return np.log(np.asarray(rows, dtype=np.float64)).astype(np.float32)
-
-
 def test_label_mass_beats_the_best_path(dev):
     """Two frames of p(a) = 0.4, p(blank) = 0.6: the best path is blank blank (0.36), the string "a" has 0.64."""
     x = _from_probs([[0.4, 0.6], [0.4, 0.6]])
@@ -233,10 +202,6 @@ def test_pruned_regime_matches_the_float64_oracle(dev, shape):
 def _iso_inputs():
     rng = np.random.default_rng(77)
     return [_noise(rng, T, 6, 5, 2.5) for T in (13, 1, 9, 14, 5)]
-
-
-def _same(a, b):
-    return all(np.array_equal(x, y, equal_nan=False) for x, y in zip(a, b))
 
 
 def test_each_utterance_alone_equals_itself_in_a_batch_bit_for_bit(dev):

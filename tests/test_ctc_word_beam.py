@@ -22,6 +22,7 @@ from silent_speech_amd import torch_ops
 from silent_speech_amd.architecture import Model
 from tests import ctc_word_beam_oracle as oracle
 from tests.backend import dev, is_emu  # noqa: F401
+from tests.ctc_beam_helpers import from_probs as _from_probs, layout as _layout, noise as _noise, same as _same, strings as _strings
 
 EXACT_BAR = (6 + 3) * 3 * 2.0 ** -19
 ALPHA, BETA = 0.8, 0.5
@@ -32,40 +33,12 @@ def _tables(lm, dev):
     return (lm.lex_child, lm.lex_word, lm.uni, lm.bi_keys, lm.bi_val, lm.tri_keys, lm.tri_val, lm.n_words, lm.start, lm.bi_probe, lm.tri_probe)
 
 
-def _search(dev, lm, utts, W, n_best, alpha=ALPHA, beta=BETA, layout='packed', ld=None, gaps=None, blank=None, space=None):
-    """utts: list of (T_i, V) float32 arrays.  layout 'packed': back to back, or with gaps[i] NaN rows in front of utterance i; 'slots': slot b
-    starts at b * T_max, NaN filler.  ld > V: NaN in the extra columns.  Returns numpy (labels, lengths, scores, ctc scores, complete)."""
-    V = utts[0].shape[1]
-    ld = ld or V
-    frames = [int(x.shape[0]) for x in utts]
-    if layout == 'slots':
-        first = [b * max(frames) for b in range(len(utts))]
-        rows = len(utts) * max(frames)
-    else:
-        gaps = gaps or [0] * len(utts)
-        first, at = [], 0
-        for g, n in zip(gaps, frames):
-            first.append(at + g)
-            at += g + n
-        rows = at
-    flat = np.full((rows, ld), np.nan, dtype=np.float32)
-    for f0, x in zip(first, utts):
-        flat[f0:f0 + x.shape[0], :V] = x
-    utt = torch.tensor([[f, n] for f, n in zip(first, frames)], dtype=torch.int64).reshape(len(utts), 2).to(dev)
-    out = torch.ops.silent_speech.ctc_word_beam_search(torch.from_numpy(flat).to(dev), utt, V, V - 1 if blank is None else blank, V - 2 if space is None else space,
-                                                       sum(frames), max(max(frames), 1), W, n_best, *_tables(lm, dev), alpha, beta)
+def _search(dev, lm, utts, W, n_best, alpha=ALPHA, beta=BETA, blank=None, space=None, **how):
+    """utts: list of (T_i, V) float32 arrays, laid out by ctc_beam_helpers.layout(**how).  Returns numpy (labels, lengths, scores, ctc scores, complete)."""
+    flat, utt, V, total, longest = _layout(dev, utts, **how)
+    out = torch.ops.silent_speech.ctc_word_beam_search(flat, utt, V, V - 1 if blank is None else blank, V - 2 if space is None else space,
+                                                       total, longest, W, n_best, *_tables(lm, dev), alpha, beta)
     return tuple(t.cpu().numpy() for t in out)
-
-
-def _strings(out, b):
-    labels, lengths = out[0], out[1]
-    return [tuple(labels[b, r, :lengths[b, r]].tolist()) for r in range(lengths.shape[1]) if lengths[b, r] >= 0]
-
-
-def _noise(rng, T, V, blank, s):
-    x = rng.standard_normal((T, V)) * s
-    x[:, blank] += s
-    return x.astype(np.float32)
 
 
 def _chars(V):
@@ -356,10 +329,6 @@ def test_lookup_wraps_around_the_table_end_and_walks_the_longest_probe(dev):
 
 
 # ---------------------------------------------------------------------------------------------- 5. semantics
-def _from_probs(rows):
-    return np.log(np.asarray(rows, dtype=np.float64)).astype(np.float32)
-
-
 def test_best_path_spells_a_non_word_and_the_result_is_the_best_lexicon_word(dev):
     """Classes a, b, space, blank; the words ab and ba.  The frames say a, blank, a: the plain search returns "aa", which is no word."""
     lm = _hand_lm(4, [(0, 1), (1, 0)])
@@ -426,10 +395,6 @@ def test_a_complete_entry_outranks_a_better_scoring_incomplete_one(dev):
 def _iso_case():
     rng = np.random.default_rng(77)
     return _random_lm(6, 12, 3, 5), [_noise(rng, T, 6, 5, 2.5) for T in (13, 1, 9, 14, 5)]
-
-
-def _same(a, b):
-    return all(np.array_equal(x, y, equal_nan=False) for x, y in zip(a, b))
 
 
 def test_each_utterance_alone_equals_itself_in_a_batch_bit_for_bit(dev):
