@@ -30,9 +30,9 @@ extern "C" {
 const char* ss_last_error(void);
 /* Library/ABI version and the GPU architecture the kernels were compiled for ("gfx950"). */
 /* Bumped whenever a struct layout or an entry-point signature changes (3: ss_gemm_epilogue column-statistics fields, the plan /
- * attention-image / LayerNorm-workspace entry points, ss_dtw_cumulative; 4: ss_loss_index_tables; 5: gate recomputation arguments of ss_bn_backward_sums / ss_bn_backward_apply; 7: ss_split_planes / ss_gemm_planes, ss_dw_job.flags, up to 24 jobs per grouped launch; 8: ss_stft_logmel_fft, the rejected-frame counter behind the matrix of ss_phoneme_confusion; 9: planes_hi / planes_lo / planes_only of ss_gemm_epilogue, dropout groups of the GEMM epilogue are row-major; 10: ss_emg_features_batch; 11: the ss_voc_* vocoder entry points; 12: the ragged-batch inference entry points ss_bn_apply_ragged, ss_relpos_attention_forward_ragged, ss_plan_forward_ragged; 13: ss_ctc_beam_search / ss_ctc_beam_workspace_bytes; 14: ss_word_lm, ss_ctc_word_beam_search / ss_ctc_word_beam_workspace_bytes, ss_word_ngram_score; 15: ss_audio_resample_batch / ss_audio_resample_supported / ss_audio_resample_limits, ss_audio_level_batch; 16: ss_spectral_gate_profile / ss_spectral_gate_batch / ss_spectral_gate_limits; 17: ss_stft_logmel_fft_backward / ss_stft_logmel_fft_backward_workspace_bytes; 18: ss_ctc_align / ss_ctc_align_workspace_bytes; 19: ss_spectral_gate_ns_batch).  Bindings must compare it with SS_ABI_VERSION at load time: a stale
+ * attention-image / LayerNorm-workspace entry points, ss_dtw_cumulative; 4: ss_loss_index_tables; 5: gate recomputation arguments of ss_bn_backward_sums / ss_bn_backward_apply; 7: ss_split_planes / ss_gemm_planes, ss_dw_job.flags, up to 24 jobs per grouped launch; 8: ss_stft_logmel_fft, the rejected-frame counter behind the matrix of ss_phoneme_confusion; 9: planes_hi / planes_lo / planes_only of ss_gemm_epilogue, dropout groups of the GEMM epilogue are row-major; 10: ss_emg_features_batch; 11: the ss_voc_* vocoder entry points; 12: the ragged-batch inference entry points ss_bn_apply_ragged, ss_relpos_attention_forward_ragged, ss_plan_forward_ragged; 13: ss_ctc_beam_search / ss_ctc_beam_workspace_bytes; 14: ss_word_lm, ss_ctc_word_beam_search / ss_ctc_word_beam_workspace_bytes, ss_word_ngram_score; 15: ss_audio_resample_batch / ss_audio_resample_supported / ss_audio_resample_limits, ss_audio_level_batch; 16: ss_spectral_gate_profile / ss_spectral_gate_batch / ss_spectral_gate_limits; 17: ss_stft_logmel_fft_backward / ss_stft_logmel_fft_backward_workspace_bytes; 18: ss_ctc_align / ss_ctc_align_workspace_bytes; 19: ss_spectral_gate_ns_batch; 20: ss_iir_filtfilt / ss_iir_filtfilt_workspace_bytes / ss_linear_resample / ss_reflect_pad removed, a single signal is a batch of one).  Bindings must compare it with SS_ABI_VERSION at load time: a stale
  * library paired with newer headers would otherwise read garbage struct fields instead of failing. */
-#define SS_ABI_VERSION 19
+#define SS_ABI_VERSION 20
 int ss_abi_version(void);
 const char* ss_target_arch(void);
 
@@ -474,10 +474,9 @@ int ss_concat_pad(const void* table_dev, int n, void* out, int64_t total_bytes, 
 /* mel target extraction (data_utils.py:39-62): reflect pad (:51); the STFT itself is ss_gemm against a
  * windowed DFT matrix with overlapping hop-strided rows; magnitude (:57); mel matmul + log clamp (:59-60)
  * is ss_gemm with epilogue.log_clamp. */
-int ss_reflect_pad(const float* y, float* out, int B, int L, int pad, int64_t ld_out, void* stream);
-/* Ragged batch (data_utils.py:76 np.clip + :51 reflect pad for EVERY utterance of a batch in one launch): utterance b is
+/* data_utils.py:76 np.clip + :51 reflect pad for EVERY utterance of a ragged batch in one launch: utterance b is
  * y[offsets_dev[b] .. + lengths_dev[b]); row b of out[B][ld_out] gets its clipped (clip != 0), reflect-padded signal and zeros
- * behind it.  min_len = the shortest length (host-known; reflect needs pad < length). */
+ * behind it.  min_len = the shortest length (host-known; reflect needs pad < length).  A (B, L) matrix is offsets b * row stride. */
 int ss_reflect_pad_ragged(const float* y, const int64_t* offsets_dev, const int32_t* lengths_dev, float* out, int B, int min_len,
                           int pad, int64_t ld_out, int clip, void* stream);
 int ss_stft_magnitude(const float* spec, int64_t ld_spec, int n_bins, float* mag, int64_t ld_mag, int rows, void* stream);
@@ -584,18 +583,16 @@ int ss_relpos_attention_x3_backward(const void* qkv_hi, const void* qkv_lo, cons
 /* ---------------------------------------------------------------------------------------------
  * Offline EMG conditioning ("next" row N4): the zero-phase IIR cascade of read_emg.py:27-38 (7 x filtfilt(iirnotch(60 h, 30)) then
  * filtfilt(butter(3, 2 Hz, 'highpass')), scipy.signal.filtfilt defaults: odd extension of 3 max(len a, len b) samples, lfilter_zi
- * initial conditions) and the np.interp resampling of read_emg.py:40-44, in f64 like numpy.  x, y: (T, C) f64, time-major.
+ * initial conditions) and the np.interp resampling of read_emg.py:40-44, in f64 like numpy, for a RAGGED BATCH of R >= 1 recordings
+ * (one launch sequence for all of them; a single recording is R = 1).  x / y are the recordings back to back, each (T_u, C) f64
+ * time-major, packed (sum T_u, C); lengths_host = the R lengths (host memory, like coef).  Work items are (chunk, channel) pairs
+ * over all recordings.
  * coef [host]: per filter 13 doubles { b[4], a[4] (a[0] = 1, zero padded), zi[3] (scipy.signal.lfilter_zi), order n, padlen }. */
-int64_t ss_iir_filtfilt_workspace_bytes(int T, int C, int max_padlen); /* [host] */
-int ss_iir_filtfilt(const double* x, double* y, int T, int C, int n_filt, const double* coef, void* workspace, int64_t workspace_bytes, void* stream);
-/* y[i] = np.interp(i / new_freq, arange(T) / old_freq, x[:, c]) for i < T_out (the caller sizes T_out = len(arange(0, (T-1)/old_freq, 1/new_freq))) */
-int ss_linear_resample(const double* x, double* y, int T, int C, double old_freq, double new_freq, int T_out, void* stream);
-/* The same for a RAGGED BATCH of recordings (one launch sequence for all of them): x / y are the recordings back to back, packed
- * (sum T_u, C) f64; lengths_host = the R lengths (host memory, like coef).  Work items are (chunk, channel) pairs over all recordings. */
 int64_t ss_iir_filtfilt_batch_workspace_bytes(const int32_t* lengths_host, int R, int C, int max_padlen, int n_filt); /* [host] */
 int ss_iir_filtfilt_batch(const double* x, double* y, const int32_t* lengths_host, int R, int C, int n_filt, const double* coef,
                           void* workspace, int64_t workspace_bytes, void* stream);
-/* np.interp of every recording onto its own grid; table_dev: int64 [R][4] = {first input row, T, first output row, T_out}. */
+/* y[i] = np.interp(i / new_freq, arange(T) / old_freq, x[:, c]) for i < T_out, every recording onto its own grid; table_dev: int64 [R][4] =
+ * {first input row, T, first output row, T_out} (the caller sizes T_out = len(arange(0, (T-1)/old_freq, 1/new_freq))). */
 int ss_linear_resample_batch(const double* x, double* y, const int64_t* table_dev, int R, int C, double old_freq, double new_freq,
                              int64_t total_out_rows, void* stream);
 /* The 14 hand-crafted features per channel of data_utils.get_emg_features (data_utils.py:85-136) for a RAGGED BATCH in one launch: x packed

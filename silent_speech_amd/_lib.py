@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.environ.get('SS_AMD_LIBRARY') or os.path.join(_HERE, 'lib', 'libsilent_speech_hip.so')      # override: A/B runs of two builds on one box
 
 SS_F32, SS_BF16, SS_F64, SS_F32X3 = 0, 1, 2, 3
-ABI_VERSION = 19         # include/silent_speech_hip.h: SS_ABI_VERSION (struct layouts / signatures this binding was written against)
+ABI_VERSION = 20         # include/silent_speech_hip.h: SS_ABI_VERSION (struct layouts / signatures this binding was written against)
 OP_KC, OP_OC = 0, 1
 
 
@@ -114,9 +114,6 @@ SIGNATURES = {
     'ss_adamw_step': [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _F, _P],
     'ss_cast_f32': [_P, _P, _I, _L, _P],
     'ss_soft_clip': [_P, _P, _L, _I, _P, _P, _F, _F, _P],
-    'ss_reflect_pad': [_P, _P, _I, _I, _I, _L, _P],
-    'ss_iir_filtfilt': [_P, _P, _I, _I, _I, _P, _P, _L, _P],
-    'ss_linear_resample': [_P, _P, _I, _I, ctypes.c_double, ctypes.c_double, _I, _P],
     'ss_iir_filtfilt_batch': [_P, _P, _P, _I, _I, _I, _P, _P, _L, _P],
     'ss_linear_resample_batch': [_P, _P, _P, _I, _I, ctypes.c_double, ctypes.c_double, _L, _P],
     'ss_emg_features_batch': [_P, _P, _P, _I, _I, _L, _P],
@@ -137,7 +134,6 @@ _HOST_FUNCS = {'ss_stft_logmel_fft_backward_workspace_bytes': ([_I, _I], ctypes.
                'ss_dtw_workspace_bytes': ([_I, _I, _LP, _LP, _LP], ctypes.c_int64),
                'ss_dtw_source': ([_I, _I, _L, _L], ctypes.c_int),
                'ss_bn_scratch_floats': ([_I, _I, _I], ctypes.c_int64),
-               'ss_iir_filtfilt_workspace_bytes': ([_I, _I, _I], ctypes.c_int64),
                'ss_iir_filtfilt_batch_workspace_bytes': ([_P, _I, _I, _I, _I], ctypes.c_int64),
                'ss_colsum_scratch_floats': ([_I, _I], ctypes.c_int64),
                'ss_audio_resample_supported': ([_I, _I, _I, _I], ctypes.c_int),

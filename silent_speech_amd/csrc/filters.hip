@@ -5,12 +5,15 @@
 //     subsample        read_emg.py:40-44   np.interp onto the 689.06 Hz / 516.79 Hz grids
 // All arithmetic is f64 like numpy's.  An IIR recurrence is sequential in time, so each filtfilt pass is parallelised by CHUNKS:
 // scipy's transposed-direct-form-II recurrence is linear in its state, z' = A z + B x, y = b0 x + z0, hence
-//   1. every chunk of L samples is run from a zero state -> its end state p_k                          (chunk_state_kernel)
-//   2. the true chunk-initial states follow from s_{k+1} = A^L s_k + p_k, s_0 = zi * x_ext[0]            (prefix_kernel, serial in k, tiny)
-//   3. every chunk is re-run from its true initial state and writes its outputs                          (apply_kernel)
+//   1. every chunk of L samples is run from a zero state -> its end state p_k                          (chunk_state_ragged_kernel)
+//   2. the true chunk-initial states follow from s_{k+1} = A^L s_k + p_k, s_0 = zi * x_ext[0]            (prefix_ragged_kernel, serial in k, tiny)
+//   3. every chunk is re-run from its true initial state and writes its outputs                          (apply_ragged_kernel)
 // with A^L computed on the host.  The backward pass is the same three kernels on the reversed index; scipy's odd extension
 // (padlen = 3 max(len a, len b)) and its initial conditions (lfilter_zi) are reproduced exactly, so results agree with
 // scipy.signal.filtfilt to f64 round-off (the chunking changes the order of a few additions).
+// There is ONE form of every kernel, the ragged batch: R recordings of different lengths back to back, a small device table in front of
+// the arithmetic.  A single recording is a batch with R = 1 (read_emg.py calls it that way); chunk boundaries are relative to each
+// recording's own extended signal, so a recording's result does not depend on what else is in the batch.
 #include "common.h"
 #include "silent_speech_hip.h"
 #include <math.h>
@@ -21,27 +24,12 @@
 #pragma clang fp contract(off)
 
 namespace {
-constexpr int FL_MIN = 256, FL_MAX = 4096;   // samples per chunk: chosen per filter, see ss_iir_filtfilt
+constexpr int FL_MIN = 256, FL_MAX = 4096;   // samples per chunk: chosen per filter, see make_filt
 constexpr int FN = 3;              // maximum state dimension (order-3 Butterworth)
 
 struct Filt { double b[FN + 1], a[FN + 1], zi[FN], AL[FN][FN]; int n, padlen, L; };
 
 __device__ __forceinline__ long long fidx(long long t, long long Te, int rev) { return rev ? Te - 1 - t : t; }
-
-// x (T, C) -> odd extension (T + 2 padlen, C); src may carry `skip` leading rows of a previous extension
-__global__ void ext_kernel(const double* __restrict__ src, long long skip, double* __restrict__ dst, int T, int C, int padlen)
-{
-    const long long Te = (long long)T + 2 * padlen, total = Te * C;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const int c = (int)(i % C); const long long t = i / C;
-        const double* x = src + skip * C + c;
-        double v;
-        if (t < padlen) v = 2.0 * x[0] - x[(long long)(padlen - t) * C];
-        else if (t < padlen + T) v = x[(t - padlen) * C];
-        else v = 2.0 * x[(long long)(T - 1) * C] - x[(long long)(T - 2 - (t - padlen - T)) * C];
-        dst[i] = v;
-    }
-}
 
 __device__ __forceinline__ double tdf2_step(const Filt& f, double x, double (&z)[FN]) {
     const double y = f.b[0] * x + z[0];
@@ -78,82 +66,7 @@ __device__ __forceinline__ void iir_walk(long long t0, long long t1, GET&& get, 
     }
 }
 
-__global__ void chunk_state_kernel(const double* __restrict__ x, int Te, int C, int nchunks, int rev, Filt f, double* __restrict__ P)
-{
-    const int c = threadIdx.x % C, k = blockIdx.x * (blockDim.x / C) + threadIdx.x / C;
-    if (k >= nchunks || threadIdx.x >= blockDim.x / C * C) return;
-    double z[FN] = {0.0, 0.0, 0.0};
-    const long long t0 = (long long)k * f.L, t1 = min((long long)Te, t0 + f.L);
-    iir_walk(t0, t1, [&](long long t) { return x[fidx(t, Te, rev) * C + c]; }, [&](long long, double v) { tdf2_step(f, v, z); });
-#pragma unroll
-    for (int i = 0; i < FN; ++i) P[((long long)k * C + c) * FN + i] = z[i];
-}
-
-__global__ void prefix_kernel(const double* __restrict__ x, int Te, int C, int nchunks, int rev, Filt f, const double* __restrict__ P, double* __restrict__ S)
-{
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    const double x0 = x[fidx(0, Te, rev) * C + c];
-    double s[FN];
-#pragma unroll
-    for (int i = 0; i < FN; ++i) s[i] = i < f.n ? f.zi[i] * x0 : 0.0;
-    for (int k = 0; k < nchunks; ++k) {
-        double nx[FN];
-#pragma unroll
-        for (int i = 0; i < FN; ++i) {
-            S[((long long)k * C + c) * FN + i] = s[i];
-            double acc = P[((long long)k * C + c) * FN + i];
-#pragma unroll
-            for (int j = 0; j < FN; ++j) acc += f.AL[i][j] * s[j];
-            nx[i] = acc;
-        }
-        // the last chunk may be shorter than L: its end state is never used
-#pragma unroll
-        for (int i = 0; i < FN; ++i) s[i] = nx[i];
-    }
-}
-
-__global__ void apply_kernel(const double* __restrict__ x, double* __restrict__ y, int Te, int C, int nchunks, int rev, Filt f, const double* __restrict__ S)
-{
-    const int c = threadIdx.x % C, k = blockIdx.x * (blockDim.x / C) + threadIdx.x / C;
-    if (k >= nchunks || threadIdx.x >= blockDim.x / C * C) return;
-    double z[FN];
-#pragma unroll
-    for (int i = 0; i < FN; ++i) z[i] = S[((long long)k * C + c) * FN + i];
-    const long long t0 = (long long)k * f.L, t1 = min((long long)Te, t0 + f.L);
-    iir_walk(t0, t1, [&](long long t) { return x[fidx(t, Te, rev) * C + c]; }, [&](long long t, double v) { y[fidx(t, Te, rev) * C + c] = tdf2_step(f, v, z); });
-}
-
-__global__ void crop_kernel(const double* __restrict__ src, long long skip, double* __restrict__ dst, int T, int C)
-{
-    const long long total = (long long)T * C;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) dst[i] = src[skip * C + i];
-}
-
-// np.interp(sample_times, times, x) with times[j] = j / old_freq, sample_times[i] = i / new_freq   (read_emg.py:40-44)
-__global__ void resample_kernel(const double* __restrict__ x, double* __restrict__ y, int T, int C, double old_freq, double new_freq, int T_out)
-{
-    const long long total = (long long)T_out * C;
-    const double step = 1.0 / new_freq;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const int c = (int)(i % C); const long long o = i / C;
-        const double t = (double)o * step;
-        long long j = (long long)(t * old_freq);
-        if (j > T - 1) j = T - 1;
-        while (j > 0 && (double)j / old_freq > t) --j;               // numpy searches the xp VALUES: settle rounding at chunk boundaries the same way
-        while (j + 1 < T && (double)(j + 1) / old_freq <= t) ++j;
-        double v;
-        if (j >= T - 1) v = x[(long long)(T - 1) * C + c];
-        else {
-            const double x0 = (double)j / old_freq, x1 = (double)(j + 1) / old_freq, f0 = x[j * C + c], f1 = x[(j + 1) * C + c];
-            const double slope = (f1 - f0) / (x1 - x0);
-            v = slope * (t - x0) + f0;
-        }
-        y[i] = v;
-    }
-}
-
-// ---- ragged batch: R recordings of different lengths through the same cascade in ONE launch sequence.  Recording u occupies rows
+// ---- R recordings of different lengths through the same cascade in ONE launch sequence.  Recording u occupies rows
 // [sum T_<u, +T_u) of the packed (sum T, C) input / output; per filter a small device table says where its extended copy, its chunks
 // and its source sit.  Work items are (chunk, channel) pairs over ALL recordings, found by binary search in the table.
 struct RagRow { long long src_off, T, ext_off, Te, chunk_off, nch; };     // elements (doubles) / rows / chunks
@@ -168,6 +81,7 @@ __device__ __forceinline__ int rag_find_chunk(const RagRow* __restrict__ tab, in
     while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (tab[mid].chunk_off <= g) lo = mid; else hi = mid - 1; }
     return lo;
 }
+// x (T, C) -> odd extension (T + 2 padlen, C) of every recording; src_off skips the leading padlen rows of the previous filter's extension
 __global__ void ext_ragged_kernel(const double* __restrict__ src, double* __restrict__ dst, const RagRow* __restrict__ tab, int R, int C, int padlen, long long total)
 {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
@@ -240,7 +154,9 @@ __global__ void crop_ragged_kernel(const double* __restrict__ src, double* __res
         dst[i] = src[tab[lo].ext_off + (long long)padlen * C + (i - tout[lo].src_off)];
     }
 }
-// tab4[u] = {in_off (rows), T, out_off (rows), T_out}: np.interp per recording onto its own grid
+// np.interp(sample_times, times, x) with times[j] = j / old_freq, sample_times[i] = i / new_freq (read_emg.py:40-44), per recording onto its
+// own grid: tab4[u] = {in_off (rows), T, out_off (rows), T_out}.  numpy searches the xp VALUES: the two while loops settle the rounding of
+// the first guess for j the same way.
 __global__ void resample_ragged_kernel(const double* __restrict__ x, double* __restrict__ y, const long long* __restrict__ tab4, int R, int C, double old_freq, double new_freq, long long total_out_rows)
 {
     const long long total = total_out_rows * C;
@@ -297,61 +213,7 @@ static int make_filt(const double* cf, int q, Filt& f)
 
 }  // namespace
 
-extern "C" int64_t ss_iir_filtfilt_workspace_bytes(int T, int C, int max_padlen)
-{
-    if (T <= 0 || C <= 0) return 0;
-    const long long Te = (long long)T + 2 * max_padlen, nch = (Te + FL_MIN - 1) / FL_MIN;
-    return (2 * Te * C + 2 * nch * C * FN) * 8 + 1024;
-}
-
-// coef: n_filt x { b[4], a[4], zi[3], n (as double), padlen (as double) } = 13 doubles per filter, host memory
-extern "C" int ss_iir_filtfilt(const double* x, double* y, int T, int C, int n_filt, const double* coef, void* workspace, int64_t workspace_bytes, void* stream)
-{
-    SS_CHECK(x && y && coef && workspace, "ss_iir_filtfilt: null pointer");
-    SS_CHECK(T > 0 && C > 0 && C <= 64 && n_filt >= 1 && n_filt <= 16, "ss_iir_filtfilt: bad sizes");
-    int max_pad = 0;
-    for (int q = 0; q < n_filt; ++q) { const int pl = (int)coef[q * 13 + 12]; SS_CHECK(pl >= 1 && pl < T, "ss_iir_filtfilt: the signal must be longer than padlen = %d", pl); max_pad = pl > max_pad ? pl : max_pad; }
-    SS_CHECK(workspace_bytes >= ss_iir_filtfilt_workspace_bytes(T, C, max_pad), "ss_iir_filtfilt: workspace too small");
-    const long long Temax = (long long)T + 2 * max_pad, nchmax = (Temax + FL_MIN - 1) / FL_MIN;
-    double* bufA = (double*)workspace; double* bufB = bufA + Temax * C; double* P = bufB + Temax * C; double* S = P + nchmax * C * FN;
-    const double* src = x; long long skip = 0;
-    const int tpb = 256 / C * C;                 // whole (chunk, channel) groups per block
-    for (int q = 0; q < n_filt; ++q) {
-        Filt f;
-        if (make_filt(coef + q * 13, q, f)) return 1;      // coefficients, chunk length L and A^L
-        const int Te = T + 2 * f.padlen, nch = (Te + f.L - 1) / f.L;
-        const long long tot = (long long)Te * C;
-        int eg = (int)((tot + 255) / 256); if (eg > 4096) eg = 4096;
-        double* E = src == bufA ? bufB : bufA;    // the extension never overwrites the buffer it reads
-        double* F = E == bufA ? bufB : bufA;
-        SS_LAUNCH(ext_kernel, dim3(eg), dim3(256), 0, stream, src, skip, E, T, C, f.padlen);
-        const int cpb = tpb / C, blocks = (nch + cpb - 1) / cpb;
-        for (int rev = 0; rev < 2; ++rev) {
-            const double* in = rev ? F : E; double* out = rev ? E : F;
-            SS_LAUNCH(chunk_state_kernel, dim3(blocks), dim3(256), 0, stream, in, Te, C, nch, rev, f, P);
-            SS_LAUNCH(prefix_kernel, dim3((C + 63) / 64), dim3(64), 0, stream, in, Te, C, nch, rev, f, (const double*)P, S);
-            SS_LAUNCH(apply_kernel, dim3(blocks), dim3(256), 0, stream, in, out, Te, C, nch, rev, f, (const double*)S);
-        }
-        src = E; skip = f.padlen;                // the filtered signal sits in E[padlen : padlen + T]
-    }
-    { const long long tot = (long long)T * C; int g = (int)((tot + 255) / 256); if (g > 4096) g = 4096;
-      SS_LAUNCH(crop_kernel, dim3(g), dim3(256), 0, stream, src, skip, y, T, C); }
-    SS_LAUNCH_CHECK("ss_iir_filtfilt");
-    return 0;
-}
-
-extern "C" int ss_linear_resample(const double* x, double* y, int T, int C, double old_freq, double new_freq, int T_out, void* stream)
-{
-    SS_CHECK(x && y, "ss_linear_resample: null pointer");
-    SS_CHECK(T >= 1 && C >= 1 && T_out >= 0 && old_freq > 0 && new_freq > 0, "ss_linear_resample: bad sizes");
-    if (T_out == 0) return 0;
-    const long long tot = (long long)T_out * C; int g = (int)((tot + 255) / 256); if (g > 4096) g = 4096;
-    SS_LAUNCH(resample_kernel, dim3(g), dim3(256), 0, stream, x, y, T, C, old_freq, new_freq, T_out);
-    SS_LAUNCH_CHECK("ss_linear_resample");
-    return 0;
-}
-
-// ---------------------------------------------------------------- ragged batch entry points
+// ---------------------------------------------------------------- entry points
 static long long rag_ext_rows(const int32_t* lengths, int R, int pad) { long long t = 0; for (int u = 0; u < R; ++u) t += (long long)lengths[u] + 2 * pad; return t; }
 static long long rag_chunks(const int32_t* lengths, int R, int pad, int L) { long long n = 0; for (int u = 0; u < R; ++u) n += ((long long)lengths[u] + 2 * pad + L - 1) / L; return n; }
 
@@ -363,6 +225,7 @@ extern "C" int64_t ss_iir_filtfilt_batch_workspace_bytes(const int32_t* lengths_
 }
 
 // x, y: packed (sum T_u, C) f64 (recording u = rows [sum T_<u, + T_u)); lengths_host: R ints (host memory, like coef)
+// coef: n_filt x { b[4], a[4], zi[3], n (as double), padlen (as double) } = 13 doubles per filter, host memory
 extern "C" int ss_iir_filtfilt_batch(const double* x, double* y, const int32_t* lengths_host, int R, int C, int n_filt, const double* coef, void* workspace, int64_t workspace_bytes, void* stream)
 {
     SS_CHECK(x && y && coef && workspace && lengths_host, "ss_iir_filtfilt_batch: null pointer");

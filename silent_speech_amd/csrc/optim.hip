@@ -89,29 +89,9 @@ extern "C" int ss_soft_clip(const float* x, float* out, int64_t n, int C, const 
 }
 
 // ---------------------------------------------------------------- mel targets: reflect padding and |STFT|
-// data_utils.py:51  F.pad(y, (p, p), mode='reflect')
-__global__ void reflect_pad_kernel(const float* __restrict__ y, float* __restrict__ out, int B, int L, int pad, long long ld_out)
-{
-    const int Lp = L + 2 * pad;
-    const long long total = (long long)B * Lp;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const int b = (int)(i / Lp), t = (int)(i - (long long)b * Lp) - pad;
-        const int s = t < 0 ? -t : (t >= L ? 2 * (L - 1) - t : t);
-        out[(long long)b * ld_out + t + pad] = y[(long long)b * L + s];
-    }
-}
-extern "C" int ss_reflect_pad(const float* y, float* out, int B, int L, int pad, int64_t ld_out, void* stream)
-{
-    SS_CHECK(y && out, "ss_reflect_pad: null pointer");
-    SS_CHECK(B > 0 && L > pad && pad >= 0 && ld_out >= L + 2 * pad, "ss_reflect_pad: bad sizes (reflect needs pad < L)");
-    long long total = (long long)B * (L + 2 * pad), blocks = (total + 255) / 256; if (blocks > 4096) blocks = 4096;
-    SS_LAUNCH(reflect_pad_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, y, out, B, L, pad, (long long)ld_out);
-    SS_LAUNCH_CHECK("ss_reflect_pad");
-    return 0;
-}
-
-// The same for a RAGGED batch (one launch for every utterance of a batch): row b of `out` holds the clipped (data_utils.py:76
-// np.clip(audio, -1, 1)) and reflect-padded signal of utterance b, L_b + 2 pad samples, zeros behind it up to ld_out.
+// data_utils.py:51  F.pad(y, (p, p), mode='reflect') for a RAGGED batch (one launch for every utterance of a batch): row b of `out` holds the
+// clipped (clip != 0: data_utils.py:76 np.clip(audio, -1, 1)) and reflect-padded signal of utterance b, L_b + 2 pad samples, zeros behind it
+// up to ld_out.  A (B, L) matrix is the batch with offsets b * row stride and lengths all L.
 __global__ void reflect_pad_ragged_kernel(const float* __restrict__ y, const long long* __restrict__ offs, const int* __restrict__ lens, float* __restrict__ out,
                                           int B, int pad, long long ld_out, int clip)
 {

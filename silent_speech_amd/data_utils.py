@@ -128,19 +128,23 @@ def _mel_spectrogram_impl(y, n_fft, num_mels, sampling_rate, hop_size, win_size,
         out = torch.empty(B, num_mels, F, dtype=torch.float32, device=dev)
         if _logmel_fft(y, None, None, L, B, F, pad, False, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, out, frame_major=False):
             return out
+
+    def reflect_pad(src, row_stride, n, p, ld_out):
+        # B rows of one length n are a ragged batch whose offsets and lengths are made on the device; the kernel writes the zeros behind each row too
+        offs, lens = torch.arange(B, dtype=torch.int64, device=dev) * row_stride, torch.full((B,), n, dtype=torch.int32, device=dev)
+        out = torch.empty(B, ld_out, dtype=torch.float32, device=dev)
+        _lib.check(_lib.lib().ss_reflect_pad_ragged(_lib.ptr(src), _lib.ptr(offs), _lib.ptr(lens), _lib.ptr(out), B, n, p, ld_out, 0, _lib.stream_of(y)), 'ss_reflect_pad_ragged')
+        return out
+
     ldp = (Lp + 3) // 4 * 4
-    ypad = torch.zeros(B, ldp, dtype=torch.float32, device=dev)
-    _lib.check(_lib.lib().ss_reflect_pad(_lib.ptr(y), _lib.ptr(ypad), B, L, pad, ldp, _lib.stream_of(y)), 'ss_reflect_pad')
+    ypad = reflect_pad(y, L, L, pad, ldp)
     if center:          # torch.stft(center=True, pad_mode='reflect') (data_utils.py:54): n_fft//2 more samples, reflected off the PADDED signal
         pad2 = n_fft // 2
         if pad2 >= Lp:
             raise ValueError('signal too short for centred frames')
         Lp2 = Lp + 2 * pad2
         ldp2 = (Lp2 + 3) // 4 * 4
-        ypad2 = torch.zeros(B, ldp2, dtype=torch.float32, device=dev)
-        src = ypad if ldp == Lp else ypad[:, :Lp].contiguous()
-        _lib.check(_lib.lib().ss_reflect_pad(_lib.ptr(src), _lib.ptr(ypad2), B, Lp, pad2, ldp2, _lib.stream_of(y)), 'ss_reflect_pad')
-        ypad, Lp, ldp = ypad2, Lp2, ldp2
+        ypad, Lp, ldp = reflect_pad(ypad, ldp, Lp, pad2, ldp2), Lp2, ldp2
     if Lp < n_fft:
         raise ValueError('signal too short for one frame')
     F = 1 + (Lp - n_fft) // hop_size

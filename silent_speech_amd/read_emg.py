@@ -130,20 +130,9 @@ def _to_device_2d(signal):
 
 
 def filtfilt_cascade(filters, signal):
-    """scipy.signal.filtfilt(b, a, signal, axis=0) for every (b, a) of `filters` in turn, all channels at once."""
+    """scipy.signal.filtfilt(b, a, signal, axis=0) for every (b, a) of `filters` in turn, all channels at once: a batch of one recording."""
     x, restore = _to_device_2d(signal)
-    T, C = x.shape
-    coef = _pack_filters(filters)
-    maxpad = int(coef[:, 12].max())
-    if T <= maxpad:
-        raise ValueError('The length of the input vector x must be greater than padlen, which is %d.' % maxpad)      # scipy's message
-    L = _lib.lib()
-    nbytes = int(L.ss_iir_filtfilt_workspace_bytes(T, C, maxpad))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-    y = torch.empty_like(x)
-    rc = L.ss_iir_filtfilt(_lib.ptr(x), _lib.ptr(y), T, C, coef.shape[0], coef.ctypes.data_as(ctypes.c_void_p), _lib.ptr(ws), nbytes, _lib.stream_of(x))
-    _lib.check(rc, 'ss_iir_filtfilt')
-    return restore(y)
+    return restore(filtfilt_cascade_batch(filters, [x])[0])
 
 
 def filtfilt_cascade_batch(filters, signals):
@@ -165,7 +154,7 @@ def filtfilt_cascade_batch(filters, signals):
     coef = _pack_filters(filters)
     maxpad = int(coef[:, 12].max())
     if int(lens.min()) <= maxpad:
-        raise ValueError('The length of the input vector x must be greater than padlen, which is %d.' % maxpad)
+        raise ValueError('The length of the input vector x must be greater than padlen, which is %d.' % maxpad)      # scipy's message
     L = _lib.lib()
     lp = lens.ctypes.data_as(ctypes.c_void_p)
     nbytes = int(L.ss_iir_filtfilt_batch_workspace_bytes(lp, len(signals), C, maxpad, coef.shape[0]))
@@ -250,13 +239,7 @@ def notch_harmonics(signal, freq, sample_frequency):
 
 def subsample(signal, new_freq, old_freq):
     x, restore = _to_device_2d(signal)
-    T, C = x.shape
-    times_last = (T - 1) / old_freq
-    T_out = len(np.arange(0, times_last, 1 / new_freq))
-    y = torch.empty(T_out, C, dtype=torch.float64, device=x.device)
-    rc = _lib.lib().ss_linear_resample(_lib.ptr(x), _lib.ptr(y), T, C, float(old_freq), float(new_freq), T_out, _lib.stream_of(x))
-    _lib.check(rc, 'ss_linear_resample')
-    return restore(y)
+    return restore(subsample_batch([x], new_freq, old_freq)[0])
 
 
 def apply_to_all(function, signal_array, *args, **kwargs):
