@@ -30,9 +30,9 @@ extern "C" {
 const char* ss_last_error(void);
 /* Library/ABI version and the GPU architecture the kernels were compiled for ("gfx950"). */
 /* Bumped whenever a struct layout or an entry-point signature changes (3: ss_gemm_epilogue column-statistics fields, the plan /
- * attention-image / LayerNorm-workspace entry points, ss_dtw_cumulative; 4: ss_loss_index_tables; 5: gate recomputation arguments of ss_bn_backward_sums / ss_bn_backward_apply; 7: ss_split_planes / ss_gemm_planes, ss_dw_job.flags, up to 24 jobs per grouped launch; 8: ss_stft_logmel_fft, the rejected-frame counter behind the matrix of ss_phoneme_confusion; 9: planes_hi / planes_lo / planes_only of ss_gemm_epilogue, dropout groups of the GEMM epilogue are row-major; 10: ss_emg_features_batch; 11: the ss_voc_* vocoder entry points; 12: the ragged-batch inference entry points ss_bn_apply_ragged, ss_relpos_attention_forward_ragged, ss_plan_forward_ragged; 13: ss_ctc_beam_search / ss_ctc_beam_workspace_bytes; 14: ss_word_lm, ss_ctc_word_beam_search / ss_ctc_word_beam_workspace_bytes, ss_word_ngram_score; 15: ss_audio_resample_batch / ss_audio_resample_supported / ss_audio_resample_limits, ss_audio_level_batch; 16: ss_spectral_gate_profile / ss_spectral_gate_batch / ss_spectral_gate_limits; 17: ss_stft_logmel_fft_backward / ss_stft_logmel_fft_backward_workspace_bytes; 18: ss_ctc_align / ss_ctc_align_workspace_bytes; 19: ss_spectral_gate_ns_batch; 20: ss_iir_filtfilt / ss_iir_filtfilt_workspace_bytes / ss_linear_resample / ss_reflect_pad removed, a single signal is a batch of one).  Bindings must compare it with SS_ABI_VERSION at load time: a stale
+ * attention-image / LayerNorm-workspace entry points, ss_dtw_cumulative; 4: ss_loss_index_tables; 5: gate recomputation arguments of ss_bn_backward_sums / ss_bn_backward_apply; 7: ss_split_planes / ss_gemm_planes, ss_dw_job.flags, up to 24 jobs per grouped launch; 8: ss_stft_logmel_fft, the rejected-frame counter behind the matrix of ss_phoneme_confusion; 9: planes_hi / planes_lo / planes_only of ss_gemm_epilogue, dropout groups of the GEMM epilogue are row-major; 10: ss_emg_features_batch; 11: the ss_voc_* vocoder entry points; 12: the ragged-batch inference entry points ss_bn_apply_ragged, ss_relpos_attention_forward_ragged, ss_plan_forward_ragged; 13: ss_ctc_beam_search / ss_ctc_beam_workspace_bytes; 14: ss_word_lm, ss_ctc_word_beam_search / ss_ctc_word_beam_workspace_bytes, ss_word_ngram_score; 15: ss_audio_resample_batch / ss_audio_resample_supported / ss_audio_resample_limits, ss_audio_level_batch; 16: ss_spectral_gate_profile / ss_spectral_gate_batch / ss_spectral_gate_limits; 17: ss_stft_logmel_fft_backward / ss_stft_logmel_fft_backward_workspace_bytes; 18: ss_ctc_align / ss_ctc_align_workspace_bytes; 19: ss_spectral_gate_ns_batch; 20: ss_iir_filtfilt / ss_iir_filtfilt_workspace_bytes / ss_linear_resample / ss_reflect_pad removed, a single signal is a batch of one; 21: ss_word_state_lm, ss_ctc_word_state_beam_search / ss_ctc_word_state_beam_workspace_bytes, ss_word_state_score).  Bindings must compare it with SS_ABI_VERSION at load time: a stale
  * library paired with newer headers would otherwise read garbage struct fields instead of failing. */
-#define SS_ABI_VERSION 20
+#define SS_ABI_VERSION 21
 int ss_abi_version(void);
 const char* ss_target_arch(void);
 
@@ -425,6 +425,54 @@ int ss_ctc_word_beam_search(const float* logits, int64_t ld, int V, int blank, i
 /* out[i] = ln P(w | w2, w1) of triples[i] = (w2, w1, w) (device, int32 x3) by the device function the search uses; an id outside the tables
  * (w not in [0, n_uni), w1 / w2 not in [-1, n_uni)) gives NaN. */
 int ss_word_ngram_score(const ss_word_lm* lm, const int32_t* triples, int64_t n, float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Word language model of ANY order 1 .. 6 as context states (what KenLM calls a state): a backoff n-gram over words and the trie of their
+ * spellings, all arrays on the device, natural-log f32.  Word ids as in ss_word_lm (n_uni of them, the start context <s> among them, below 2^21).
+ * A STATE is a word context the model knows: state 0 = the empty context, state 1 + w = the context (w), further ids = every n-gram of
+ * 2 .. order - 1 words, numbered by increasing length.  A beam entry holds one state id whatever the order.
+ *   lex_child / lex_word   as in ss_word_lm.
+ *   uni_logp (n_uni)       ln P(w): the arcs out of state 0; their next state is 1 + w.
+ *   st_bo (n_states)       backoff weight of the state's context (st_bo[0] = 0).
+ *   st_shorter (n_states)  int32: the state of the longest proper suffix of the context that is a state (levels may be skipped); the builder
+ *                          guarantees st_shorter[s] < s, the kernels do not rely on it.
+ *   arc_*                  ONE open-addressing hash table for the n-grams of 2 .. order words: 64-bit key (state of the context << 21 | word), an
+ *                          all-ones key = empty slot, slot count a power of two (or 0: a unigram model), home slot = splitmix64 finaliser of
+ *                          key + 0x9E3779B97F4A7C15, & (slots - 1), linear probing that wraps around; arc_probe = the longest probe sequence
+ *                          the builder needed (<= arc_slots), the lookup's loop bound.  Beside the keys: arc_logp = ln P(word | context) and
+ *                          arc_next int32 = the state of the longest suffix of context + word that is a state.
+ * ln P(w | s) and the state after w: walk s_0 = s, s_{i+1} = st_shorter[s_i] while s_i != 0, AT MOST order - 1 steps; the first s_i with an
+ * arc for w gives p and next; without one p = uni_logp[w], next = 1 + w; the value is st_bo[s_0] + (st_bo[s_1] + ... + (st_bo[s_{i-1}] + p)),
+ * summed from the lowest order outward -- for a model of order <= 3 the same f32 number as the rule of ss_word_lm.
+ * Every index formed from these tables is checked against the sizes given here (a state, next or shorter outside [0, n_states) counts as state
+ * 0), and no loop is bounded by table contents: a malformed table gives wrong words, never a read outside the arrays or an unbounded loop.
+ * Not here: the KenLM binary format, parity with ctcdecode's own numbers, an out-of-vocabulary escape. */
+typedef struct ss_word_state_lm {
+    const int32_t* lex_child;
+    const int32_t* lex_word;
+    const float* uni_logp;
+    const float* st_bo;
+    const int32_t* st_shorter;
+    const uint64_t* arc_keys;
+    const float* arc_logp;
+    const int32_t* arc_next;
+    int32_t n_nodes, n_vocab, n_uni, n_states;
+    int32_t start_state, arc_slots, arc_probe, order;
+} ss_word_state_lm;
+
+/* ss_ctc_word_beam_search with the word model as context states (csrc/ctc_word_state_decode.hip): the same search, rules, ranking and outputs;
+ * an entry carries the state before the word it is spelling instead of (w2, w1).  start: the root and start_state.  Where an extension
+ * creates an entry whose node spells a word w, ONE lookup (state, w) gives alpha * ln P(w | state) + beta and the state after w; the space
+ * extension adds the former and moves to the latter.  1 <= order <= 6, n_states >= 1 + n_uni, start_state in [0, n_states).
+ * workspace: ss_ctc_word_state_beam_workspace_bytes(n_utt, total_frames, W) bytes; -1 = bad arguments. */
+int64_t ss_ctc_word_state_beam_workspace_bytes(int n_utt, int64_t total_frames, int beam_width);
+int ss_ctc_word_state_beam_search(const float* logits, int64_t ld, int V, int blank, int space, int64_t rows, const float* lse, const int64_t* utt_dev,
+                                  int n_utt, int64_t total_frames, int beam_width, int n_best, const ss_word_state_lm* lm, float alpha, float beta,
+                                  void* workspace, int max_len, int32_t* labels, int32_t* lengths, float* scores, float* ctc_scores,
+                                  int32_t* complete, void* stream);
+/* out_lnp[i] = ln P(word | state), out_next[i] = the state after it, of pairs[i] = (state, word) (device, int32 x2) by the device function
+ * the search uses; a state outside [0, n_states) or a word outside [0, n_uni) gives NaN and -1. */
+int ss_word_state_score(const ss_word_state_lm* lm, const int32_t* pairs, int64_t n, float* out_lnp, int32_t* out_next, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Forced alignment: the best (Viterbi) alignment of a KNOWN label string to the frame posteriors, the whole batch in one launch

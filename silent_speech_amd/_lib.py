@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.environ.get('SS_AMD_LIBRARY') or os.path.join(_HERE, 'lib', 'libsilent_speech_hip.so')      # override: A/B runs of two builds on one box
 
 SS_F32, SS_BF16, SS_F64, SS_F32X3 = 0, 1, 2, 3
-ABI_VERSION = 20         # include/silent_speech_hip.h: SS_ABI_VERSION (struct layouts / signatures this binding was written against)
+ABI_VERSION = 21         # include/silent_speech_hip.h: SS_ABI_VERSION (struct layouts / signatures this binding was written against)
 OP_KC, OP_OC = 0, 1
 
 
@@ -57,6 +57,13 @@ class WordLm(ctypes.Structure):
                 ('tri_logp', ctypes.c_void_p), ('n_nodes', ctypes.c_int32), ('n_vocab', ctypes.c_int32), ('n_uni', ctypes.c_int32),
                 ('start', ctypes.c_int32), ('bi_slots', ctypes.c_int32), ('bi_probe', ctypes.c_int32), ('tri_slots', ctypes.c_int32),
                 ('tri_probe', ctypes.c_int32)]
+
+
+class WordStateLm(ctypes.Structure):
+    _fields_ = [('lex_child', ctypes.c_void_p), ('lex_word', ctypes.c_void_p), ('uni_logp', ctypes.c_void_p), ('st_bo', ctypes.c_void_p),
+                ('st_shorter', ctypes.c_void_p), ('arc_keys', ctypes.c_void_p), ('arc_logp', ctypes.c_void_p), ('arc_next', ctypes.c_void_p),
+                ('n_nodes', ctypes.c_int32), ('n_vocab', ctypes.c_int32), ('n_uni', ctypes.c_int32), ('n_states', ctypes.c_int32),
+                ('start_state', ctypes.c_int32), ('arc_slots', ctypes.c_int32), ('arc_probe', ctypes.c_int32), ('order', ctypes.c_int32)]
 
 
 _P, _I, _F, _L = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64
@@ -110,6 +117,8 @@ SIGNATURES = {
     'ss_ctc_beam_search': [_P, _L, _I, _I, _L, _P, _P, _I, _L, _I, _I, _P, _F, _F, _P, _I, _P, _P, _P, _P, _P],
     'ss_ctc_word_beam_search': [_P, _L, _I, _I, _I, _L, _P, _P, _I, _L, _I, _I, ctypes.POINTER(WordLm), _F, _F, _P, _I, _P, _P, _P, _P, _P, _P],
     'ss_word_ngram_score': [ctypes.POINTER(WordLm), _P, _L, _P, _P],
+    'ss_ctc_word_state_beam_search': [_P, _L, _I, _I, _I, _L, _P, _P, _I, _L, _I, _I, ctypes.POINTER(WordStateLm), _F, _F, _P, _I, _P, _P, _P, _P, _P, _P],
+    'ss_word_state_score': [ctypes.POINTER(WordStateLm), _P, _L, _P, _P, _P],
     'ss_ctc_align': [_P, _L, _I, _I, _L, _P, _P, _I, _L, _I, _P, _L, _P, _P, _P, _P, _P, _P, _P],
     'ss_adamw_step': [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _F, _P],
     'ss_cast_f32': [_P, _P, _I, _L, _P],
@@ -168,6 +177,7 @@ _HOST_FUNCS = {'ss_stft_logmel_fft_backward_workspace_bytes': ([_I, _I], ctypes.
                'ss_relpos_attention_saved_bytes': ([_I, _I, _I, _I, _I, _I], ctypes.c_int64),
                'ss_ctc_beam_workspace_bytes': ([_I, _L, _I], ctypes.c_int64),
                'ss_ctc_word_beam_workspace_bytes': ([_I, _L, _I], ctypes.c_int64),
+               'ss_ctc_word_state_beam_workspace_bytes': ([_I, _L, _I], ctypes.c_int64),
                'ss_ctc_align_workspace_bytes': ([_I, _L, _I], ctypes.c_int64),
                'ss_voc_blob_bytes': ([_I, _I, _I], ctypes.c_int64),
                'ss_voc_workspace_bytes': ([_L, _I, ctypes.POINTER(ctypes.c_int), _I], ctypes.c_int64),

@@ -7,6 +7,8 @@
     LabelNgramLM                             label trigram table counted from text, the language model of the beam search
     WordNgramLM                              word n-gram with backoff (orders 1 .. 3, from ARPA text or counted from transcripts) + the lexicon of
                                              its vocabulary: beam_decode* with it run the lexicon-constrained search of csrc/ctc_word_decode.hip
+    WordStateLM                              the same of any order up to 6 (a pruned 5-gram ARPA file), held as context states: beam_decode* with it
+                                             run the search of csrc/ctc_word_state_decode.hip
     forced_align(logits, lengths, targets)   best alignment of KNOWN label strings to the frames on the device (csrc/ctc_align.hip): Alignment per
                                              utterance; forced_align_utterances for the list Model.forward_utterances returns
     word_segments(alignment, text_int, tt)   (word, start_s, end_s, confidence) of a character alignment; align(model, testset, device) for a data set
@@ -18,8 +20,8 @@ alpha/beta recursion and its gradient run in csrc/ctc.hip straight on the packed
 decollate + pad_sequence copies and the (T_max, N, V) log-prob tensor of the reference never exist.
 The search of the reference's decoder (ctcdecode, :33-35,48-49) is here as a kernel of its own: a prefix beam search over whole batches
 in one launch, with shallow fusion of a label n-gram table that lives on the device (LabelNgramLM), or -- as ctcdecode does it with a
-KenLM model -- confined to the spellings of a vocabulary with a WORD n-gram with backoff scored at every word end (WordNgramLM: orders 1 to 3,
-read from ARPA text or counted from transcripts; the search is lexicon-constrained, there is no out-of-vocabulary escape).  Out of scope: the
+KenLM model -- confined to the spellings of a vocabulary with a WORD n-gram with backoff scored at every word end (WordNgramLM: orders 1 to 3 as
+hashed n-gram keys; WordStateLM: orders 1 to 6 as KenLM-style context states; both read from ARPA text or counted from transcripts; the search is lexicon-constrained, there is no out-of-vocabulary escape).  Out of scope: the
 KenLM BINARY format (third-party C++; convert lm.binary to ARPA text) and parity with ctcdecode's own numbers, which stays unpinned because
 ctcdecode is not available to compare against.  test() reports greedy WER by default and beam-search WER with decoder='beam'.
 """
@@ -246,6 +248,94 @@ def _ngram_table(keys, values, columns, min_slots):
     return tab, val, probe
 
 
+def _read_arpa(path_or_file, max_order, who):
+    """The sections of ARPA text (\\data\\, \\1-grams: .. , \\end\\): {n: [(words tuple, ln P, ln backoff)]}, log10 -> ln, a missing backoff = 0.
+    A section or a non-zero count above max_order: ValueError in the name of `who`."""
+    f = open(path_or_file) if isinstance(path_or_file, (str, os.PathLike)) else path_or_file
+    try:
+        lines = [line.strip() for line in f]
+    finally:
+        if f is not path_or_file:
+            f.close()
+    grams, order = {k: [] for k in range(1, max_order + 1)}, 0
+    for line in lines:
+        if not line or line == '\\data\\':
+            continue
+        if line == '\\end\\':
+            break
+        if line.startswith('ngram '):
+            n, count = line[6:].split('=')
+            if int(n) > max_order and int(count) > 0:
+                raise ValueError('%s.from_arpa: order %d (orders 1 to %d are supported)' % (who, int(n), max_order))
+            continue
+        if line.startswith('\\') and line.endswith('-grams:'):
+            order = int(line[1:-7])
+            if order > max_order:
+                raise ValueError('%s.from_arpa: order %d (orders 1 to %d are supported)' % (who, order, max_order))
+            continue
+        if order == 0:
+            continue
+        f_ = line.split()
+        if len(f_) not in (order + 1, order + 2):
+            raise ValueError('%s.from_arpa: cannot read %r as a %d-gram' % (who, line, order))
+        grams[order].append((tuple(f_[1:order + 1]), float(f_[0]) * _LN10, float(f_[order + 1]) * _LN10 if len(f_) == order + 2 else 0.0))
+    return grams
+
+
+def _arpa_vocabulary(unigrams, text_transform):
+    """(words = the sorted cleaned spellings, {ARPA word: id} with '<s>' = len(words)) of the unigram section: </s> and <unk> are never predicted, a
+    word whose clean_text spelling is empty, holds a space or a character outside text_transform.chars is dropped, and of two words with one
+    cleaned spelling the one with the larger unigram probability keeps it."""
+    chars = text_transform.chars
+    best = {}                                                            # cleaned spelling -> (unigram ln P, ARPA word)
+    for (w,), lp, _ in unigrams:
+        if w in ('<s>', '</s>', '<unk>'):
+            continue
+        sp = text_transform.clean_text(w)
+        if sp and all(c != ' ' and c in chars for c in sp) and (sp not in best or lp > best[sp][0]):
+            best[sp] = (lp, w)
+    words = sorted(best)
+    ids = {best[sp][1]: i for i, sp in enumerate(words)}
+    ids['<s>'] = len(words)
+    return words, ids
+
+
+def _discounted(counts, lower, n, discount):
+    """Absolute discounting of one n-gram level: {context: {w: P}} and {context: ln backoff} from {(context..., w): count}; lower(context, w) =
+    the lower level's P, n = the vocabulary size."""
+    by = {}
+    for k, c in counts.items():
+        by.setdefault(k[:-1], {})[k[-1]] = c
+    P, BO = {}, {}
+    for h, cs in by.items():
+        total = float(sum(cs.values()))
+        rest = 1.0 - sum(lower(h, w) for w in cs)
+        if len(cs) == n or rest <= 1e-12:
+            P[h], BO[h] = {w: c / total for w, c in cs.items()}, 0.0
+        else:
+            P[h] = {w: (c - discount) / total for w, c in cs.items()}
+            BO[h] = float(np.log((1.0 - sum(P[h].values())) / rest))
+    return P, BO
+
+
+def _lexicon_trie(words, chars):
+    """The trie of the spellings: (lex_child (n_nodes, C) int32 = child node or -1, lex_word (n_nodes) int32 = the word a node spells or -1); node 0
+    is the root, label number = index into chars."""
+    C = len(chars)
+    child, word = [[-1] * C], [-1]
+    for w, spelling in enumerate(words):
+        node = 0
+        for ch in spelling:
+            c = chars.index(ch)
+            if child[node][c] < 0:
+                child[node][c] = len(child)
+                child.append([-1] * C)
+                word.append(-1)
+            node = child[node][c]
+        word[node] = w
+    return torch.from_numpy(np.asarray(child, dtype=np.int32).reshape(len(child), C)), torch.from_numpy(np.asarray(word, dtype=np.int32))
+
+
 class WordNgramLM(object):
     """Word n-gram with backoff of order 1 to 3 and the lexicon trie of its vocabulary: the language model of the lexicon-constrained beam search
     (include/silent_speech_hip.h: ss_word_lm, ss_ctc_word_beam_search).  Natural log, f32.
@@ -274,21 +364,7 @@ class WordNgramLM(object):
         self.trigrams = {(int(a), int(b), int(c)): np.float32(v) for (a, b, c), v in (trigrams or {}).items()}
         if any(not (0 <= a <= n and 0 <= b < n) for a, b in self.bigrams) or any(not (0 <= a <= n and 0 <= b < n and 0 <= c < n) for a, b, c in self.trigrams):
             raise ValueError('WordNgramLM: n-gram word ids must be below %d (the start context %d only leads)' % (n, n))
-        # the lexicon trie
-        C = len(self.chars)
-        child, word = [[-1] * C], [-1]
-        for w, spelling in enumerate(words):
-            node = 0
-            for ch in spelling:
-                c = self.chars.index(ch)
-                if child[node][c] < 0:
-                    child[node][c] = len(child)
-                    child.append([-1] * C)
-                    word.append(-1)
-                node = child[node][c]
-            word[node] = w
-        self.lex_child = torch.from_numpy(np.asarray(child, dtype=np.int32).reshape(len(child), C))
-        self.lex_word = torch.from_numpy(np.asarray(word, dtype=np.int32))
+        self.lex_child, self.lex_word = _lexicon_trie(words, self.chars)
         # the hash tables
         bk = sorted(self.bigrams)
         tk = sorted(self.trigrams)
@@ -362,45 +438,8 @@ class WordNgramLM(object):
         <unk> are read and never predicted (the search is lexicon-constrained, so n-grams holding them can never be asked for and are left out).
         A word whose clean_text spelling is empty, holds a space or a character outside text_transform.chars is dropped with every n-gram
         holding it; of two words with one cleaned spelling the one with the larger unigram probability keeps it.  Order > 3: ValueError."""
-        f = open(path_or_file) if isinstance(path_or_file, (str, os.PathLike)) else path_or_file
-        try:
-            lines = [line.strip() for line in f]
-        finally:
-            if f is not path_or_file:
-                f.close()
-        grams, order = {1: [], 2: [], 3: []}, 0
-        for line in lines:
-            if not line or line == '\\data\\':
-                continue
-            if line == '\\end\\':
-                break
-            if line.startswith('ngram '):
-                n, count = line[6:].split('=')
-                if int(n) > 3 and int(count) > 0:
-                    raise ValueError('WordNgramLM.from_arpa: order %d (orders 1 to 3 are supported)' % int(n))
-                continue
-            if line.startswith('\\') and line.endswith('-grams:'):
-                order = int(line[1:-7])
-                if order > 3:
-                    raise ValueError('WordNgramLM.from_arpa: order %d (orders 1 to 3 are supported)' % order)
-                continue
-            if order == 0:
-                continue
-            f_ = line.split()
-            if len(f_) not in (order + 1, order + 2):
-                raise ValueError('WordNgramLM.from_arpa: cannot read %r as a %d-gram' % (line, order))
-            grams[order].append((tuple(f_[1:order + 1]), float(f_[0]) * _LN10, float(f_[order + 1]) * _LN10 if len(f_) == order + 2 else 0.0))
-        chars = text_transform.chars
-        best = {}                                                            # cleaned spelling -> (unigram ln P, ARPA word)
-        for (w,), lp, _ in grams[1]:
-            if w in ('<s>', '</s>', '<unk>'):
-                continue
-            sp = text_transform.clean_text(w)
-            if sp and all(c != ' ' and c in chars for c in sp) and (sp not in best or lp > best[sp][0]):
-                best[sp] = (lp, w)
-        words = sorted(best)
-        ids = {best[sp][1]: i for i, sp in enumerate(words)}
-        ids['<s>'] = len(words)
+        grams = _read_arpa(path_or_file, 3, 'WordNgramLM')
+        words, ids = _arpa_vocabulary(grams[1], text_transform)
         uni = np.zeros((len(words) + 1, 2), dtype=np.float64)
         uni[len(words), 0] = -99.0 * _LN10
         for (w,), lp, bo in grams[1]:
@@ -408,7 +447,7 @@ class WordNgramLM(object):
                 uni[ids[w]] = (lp, bo)
         bi = {(ids[a], ids[b]): (lp, bo) for (a, b), lp, bo in grams[2] if a in ids and b in ids and b != '<s>'}
         tri = {(ids[a], ids[b], ids[c]): lp for (a, b, c), lp, _ in grams[3] if a in ids and b in ids and c in ids and b != '<s>' and c != '<s>'}
-        return cls(words, uni, bi, tri, chars, min_slots)
+        return cls(words, uni, bi, tri, text_transform.chars, min_slots)
 
     @classmethod
     def from_texts(cls, texts, text_transform, order=3, discount=0.75, add_k=0.1, min_slots=0):
@@ -441,29 +480,13 @@ class WordNgramLM(object):
         uni = np.zeros((n + 1, 2), dtype=np.float64)
         uni[:n, 0] = np.log(p1)
         uni[n, 0] = -99.0 * _LN10
-
-        def discounted(counts, lower):
-            """{context: {w: P}} and {context: ln backoff} from {(context..., w): count}; lower(context, w) = the lower order's P."""
-            by = {}
-            for k, c in counts.items():
-                by.setdefault(k[:-1], {})[k[-1]] = c
-            P, BO = {}, {}
-            for h, cs in by.items():
-                total = float(sum(cs.values()))
-                rest = 1.0 - sum(lower(h, w) for w in cs)
-                if len(cs) == n or rest <= 1e-12:
-                    P[h], BO[h] = {w: c / total for w, c in cs.items()}, 0.0
-                else:
-                    P[h] = {w: (c - discount) / total for w, c in cs.items()}
-                    BO[h] = float(np.log((1.0 - sum(P[h].values())) / rest))
-            return P, BO
-        P2, BO1 = discounted(c2, lambda h, w: p1[w])
+        P2, BO1 = _discounted(c2, lambda h, w: p1[w], n, discount)
         for (w1,), bo in BO1.items():
             uni[w1, 1] = bo
 
         def p_bi(w1, w):
             return P2[(w1,)][w] if (w1,) in P2 and w in P2[(w1,)] else float(np.exp(uni[w1, 1])) * p1[w]
-        P3, BO2 = discounted(c3, lambda h, w: p_bi(h[1], w))
+        P3, BO2 = _discounted(c3, lambda h, w: p_bi(h[1], w), n, discount)
         bi = {(w1, w): (float(np.log(p)), BO2.get((w1, w), 0.0)) for (w1,), ps in P2.items() for w, p in ps.items()}
         tri = {(w2, w1, w): float(np.log(p)) for (w2, w1), ps in P3.items() for w, p in ps.items()}
         return cls(words, uni, bi, tri, chars, min_slots)
@@ -507,9 +530,256 @@ class WordNgramLM(object):
             return cls([str(w) for w in z['words']], z['unigrams'], bi, tri, str(z['chars']), int(z['min_slots']))
 
 
+class WordStateLM(object):
+    """Word n-gram with backoff of ANY order 1 to 6 held as context states, and the lexicon trie of its vocabulary: the language model of
+    csrc/ctc_word_state_decode.hip (include/silent_speech_hip.h: ss_word_state_lm, ss_ctc_word_state_beam_search).  Natural log, f32.
+
+    words        the vocabulary, cleaned spellings over `chars`; word id = index, the start context <s> has id n_words and may only lead an n-gram
+    ngrams       {(w_1, .., w_n): (ln P(w_n | w_1 .. w_{n-1}), backoff of the context (w_1 .. w_n))}, 1 <= n <= order; every unigram, <s> included,
+                 must be there, and the model must be PREFIX-CLOSED: the context (w_1 .. w_{n-1}) of every n-gram is itself an n-gram (KenLM and
+                 SRILM files are; dropping words with every n-gram that holds them keeps them so)
+    order        default max(2, the longest n-gram); contexts of up to order - 1 words become states
+    min_slots    least slot count of the hash table (tests force wrap-around and long probes with it)
+
+    A STATE is a context the model knows: 0 = the empty context, 1 + w = (w), then every n-gram of 2 .. order - 1 words by increasing length, so
+    shorter[s] (the state of the longest proper suffix of s that is a state) < s.  An ARC is an n-gram of >= 2 words: key (state of its context
+    << 21 | word) -> (ln P, next = the state of the longest suffix of the whole n-gram that is a state).  ln P(w | s): the first state of the chain
+    s, shorter[s], .. (0 left out) with an arc for w gives p and next, none gives the unigram and next = 1 + w; the value adds the backoffs of the
+    states passed, summed from the lowest order outward -- for order <= 3 the f32 numbers of WordNgramLM.
+
+    Device form (torch tensors, `to(device)`): lex_child (n_nodes, C) / lex_word (n_nodes) int32, uni_logp (n_words + 1) f32, st_bo (n_states) f32,
+    st_shorter (n_states) int32, arc_keys (slots) int64 + arc_logp (slots) f32 + arc_next (slots) int32; arc_probe = the longest probe sequence."""
+    MAX_WORDS = 1 << 21
+    MAX_ORDER = 6
+
+    def __init__(self, words, ngrams, chars, order=None, min_slots=0):
+        words = [str(w) for w in words]
+        n = len(words)
+        if n + 1 > self.MAX_WORDS:
+            raise ValueError('WordStateLM: %d words (< 2^21)' % n)
+        if len(set(words)) != n or any(not w or any(c == ' ' or c not in chars for c in w) for w in words):
+            raise ValueError('WordStateLM: the words must be distinct, non-empty and spelled with the labels %r without the space' % (chars,))
+        self.words, self.chars, self.min_slots = words, str(chars), int(min_slots)
+        self.ngrams = {tuple(int(w) for w in g): (np.float32(v[0]), np.float32(v[1])) for g, v in ngrams.items()}
+        longest = max((len(g) for g in self.ngrams), default=0)
+        self._order = max(2, longest) if order is None else int(order)
+        if not (1 <= longest <= self._order <= self.MAX_ORDER):
+            raise ValueError('WordStateLM: n-grams of 1 .. %d words and order %d (at most %d)' % (longest, self._order, self.MAX_ORDER))
+        if any(not g or not (0 <= g[0] <= n) or any(not (0 <= w < n) for w in g[1:]) for g in self.ngrams):
+            raise ValueError('WordStateLM: n-gram word ids must be below %d (the start context %d only leads)' % (n, n))
+        if any((w,) not in self.ngrams for w in range(n + 1)):
+            raise ValueError('WordStateLM: every unigram, the start context %d included, must be present' % n)
+        for g in self.ngrams:
+            if len(g) > 1 and g[:-1] not in self.ngrams:
+                raise ValueError('WordStateLM: the model is not prefix-closed: the context of the n-gram %r is no n-gram' % (g,))
+        self.lex_child, self.lex_word = _lexicon_trie(words, self.chars)
+        # states: the empty context, the unigrams, then the n-grams of 2 .. order - 1 words by increasing length
+        contexts = [()] + [(w,) for w in range(n + 1)] + sorted((g for g in self.ngrams if 2 <= len(g) < self._order), key=lambda g: (len(g), g))
+        self._state = {c: s for s, c in enumerate(contexts)}
+        self._contexts = contexts
+        bo = np.asarray([0.0] + [self.ngrams[c][1] for c in contexts[1:]], dtype=np.float32)
+        shorter = np.asarray([0] + [self.state_of(c[1:]) for c in contexts[1:]], dtype=np.int32)
+        # arcs: one hash table for the n-grams of >= 2 words
+        arcs = sorted(g for g in self.ngrams if len(g) >= 2)
+        keys = np.asarray([(self._state[g[:-1]] << 21) | g[-1] for g in arcs], dtype=np.uint64)
+        tab, val, self.arc_probe = _ngram_table(keys, [self.ngrams[g][0] for g in arcs], 1, min_slots)
+        nxt = np.zeros(tab.shape[0], dtype=np.int32)
+        slot = {int(k): i for i, k in enumerate(tab.tolist()) if k != int(_NGRAM_EMPTY)}
+        for g, k in zip(arcs, keys.tolist()):
+            nxt[slot[k]] = self.state_of(g)
+        self._arcs = {(self._state[g[:-1]], g[-1]): (self.ngrams[g][0], self.state_of(g)) for g in arcs}
+        self._bo, self._shorter = bo, shorter
+        self.uni_logp = torch.from_numpy(np.asarray([self.ngrams[(w,)][0] for w in range(n + 1)], dtype=np.float32))
+        self.st_bo, self.st_shorter = torch.from_numpy(bo), torch.from_numpy(shorter)
+        self.arc_keys, self.arc_logp, self.arc_next = torch.from_numpy(tab.view(np.int64)), torch.from_numpy(val.reshape(-1)), torch.from_numpy(nxt)
+
+    _DEVICE_FORM = ('lex_child', 'lex_word', 'uni_logp', 'st_bo', 'st_shorter', 'arc_keys', 'arc_logp', 'arc_next')
+
+    @property
+    def n_words(self):
+        return len(self.words)
+
+    @property
+    def start(self):
+        return len(self.words)
+
+    @property
+    def start_state(self):
+        return 1 + len(self.words)
+
+    @property
+    def order(self):
+        return self._order
+
+    @property
+    def n_states(self):
+        return len(self._contexts)
+
+    def to(self, device):
+        """The same model with its tables on `device` (the host form is shared, not copied)."""
+        other = object.__new__(WordStateLM)
+        other.__dict__.update(self.__dict__)
+        for name in self._DEVICE_FORM:
+            setattr(other, name, getattr(self, name).to(device))
+        return other
+
+    def state_of(self, context_words):
+        """The state of the longest suffix of the word ids `context_words` (oldest first, at most order - 1 of them count) that is a state."""
+        c = tuple(int(w) for w in context_words)
+        c = c[max(0, len(c) - (self._order - 1)):]
+        while c not in self._state:
+            c = c[1:]
+        return self._state[c]
+
+    def context_of(self, state):
+        """The word ids of a state's context, oldest first."""
+        return self._contexts[int(state)]
+
+    def word_ids(self, text, text_transform):
+        """Ids of the words of `text` after clean_text; raises KeyError on a word outside the vocabulary."""
+        index = getattr(self, '_index', None)
+        if index is None:
+            index = self._index = {w: i for i, w in enumerate(self.words)}
+        return [index[w] for w in text_transform.clean_text(text).split()]
+
+    def score_words(self, word_ids, dtype=np.float64, context=()):
+        """ln P of every word of a sentence given the words before it -- the state rule of ss_word_state_lm restated on the host dictionaries, in
+        `dtype` arithmetic.  context: the word ids the sentence starts behind, oldest first; the default () is the sentence start (<s>), ids
+        below 0 are "no word", so (-1,) is the empty context."""
+        ctx = tuple(int(w) for w in context) if len(context) else (self.start,)
+        ctx = tuple(w for w in ctx if w >= 0)
+        if any(w > self.n_words for w in ctx):
+            raise ValueError('score_words: word id outside the model')
+        s = self.state_of(ctx)
+        out = np.zeros(len(word_ids), dtype=dtype)
+        for i, w in enumerate(word_ids):
+            w = int(w)
+            if not (0 <= w <= self.n_words):
+                raise ValueError('score_words: word id outside the model')
+            passed, at = [], s
+            while at != 0 and (at, w) not in self._arcs:
+                passed.append(at)
+                at = int(self._shorter[at])
+            p, s = (dtype(self.ngrams[(w,)][0]), 1 + w) if at == 0 else (dtype(self._arcs[(at, w)][0]), self._arcs[(at, w)][1])
+            for q in reversed(passed):
+                p = dtype(self._bo[q]) + p
+            out[i] = p
+        return out
+
+    def score_states(self, pairs):
+        """torch.ops.silent_speech.word_state_score on this model's tables: (ln P(word | state), the state after the word) of (n, 2) int32 rows
+        (state, word) on the tables' device."""
+        return torch.ops.silent_speech.word_state_score(pairs, self.uni_logp, self.st_bo, self.st_shorter, self.arc_keys, self.arc_logp, self.arc_next,
+                                                        self.arc_probe, self._order)
+
+    # ---- builders
+    @classmethod
+    def from_ngram_lm(cls, lm):
+        """The same model as a WordNgramLM, order 3 whatever it holds: every bigram is a state with its stored backoff, as the table search assumes."""
+        grams = {(w,): tuple(lm.unigrams[w]) for w in range(lm.n_words + 1)}
+        grams.update(lm.bigrams)
+        grams.update({g: (p, 0.0) for g, p in lm.trigrams.items()})
+        return cls(lm.words, grams, lm.chars, 3, lm.min_slots)
+
+    @classmethod
+    def from_arpa(cls, path_or_file, text_transform, min_slots=0):
+        """Reads ARPA text (\\data\\, \\1-grams: .. \\6-grams:, \\end\\; log10 values, a missing backoff = 0) with the rules of
+        WordNgramLM.from_arpa: <s> is the start context; </s> and <unk> are read and never predicted; a word whose clean_text spelling is empty,
+        holds a space or a character outside text_transform.chars is dropped with every n-gram holding it; of two words with one cleaned
+        spelling the one with the larger unigram probability keeps it.  Order > 6: ValueError."""
+        grams = _read_arpa(path_or_file, cls.MAX_ORDER, 'WordStateLM')
+        words, ids = _arpa_vocabulary(grams[1], text_transform)
+        out = {(w,): (0.0, 0.0) for w in range(len(words) + 1)}
+        out[(len(words),)] = (-99.0 * _LN10, 0.0)
+        for k in range(1, cls.MAX_ORDER + 1):
+            for g, lp, bo in grams[k]:
+                if all(w in ids for w in g) and '<s>' not in g[1:]:
+                    out[tuple(ids[w] for w in g)] = (lp, bo)
+        return cls(words, out, text_transform.chars, None, min_slots)
+
+    @classmethod
+    def from_texts(cls, texts, text_transform, order=3, discount=0.75, add_k=0.1, min_slots=0):
+        """WordNgramLM.from_texts for any order up to 6 (for order <= 3 the same f32 numbers): unigrams add-k over the vocabulary, every higher
+        level absolute discounting, P(w | h) = (c(h w) - discount) / c(h .), the backoff weight of every seen context giving the rest to the
+        next lower level so that the probabilities over the vocabulary sum to 1."""
+        if order not in range(1, cls.MAX_ORDER + 1) or not (0 < discount < 1) or not add_k > 0:
+            raise ValueError('WordStateLM.from_texts: order 1 .. %d, 0 < discount < 1 and add_k > 0' % cls.MAX_ORDER)
+        chars = text_transform.chars
+        sents = [[w if all(c in chars for c in w) else None for w in text_transform.clean_text(t).split()] for t in texts]
+        words = sorted({w for s in sents for w in s if w is not None})
+        n = len(words)
+        ids = {w: i for i, w in enumerate(words)}
+        c1, counts = np.zeros(n, dtype=np.float64), {k: {} for k in range(2, order + 1)}
+        for s in sents:
+            seq = [n] + [ids[w] if w is not None else None for w in s]
+            for i in range(1, len(seq)):
+                if seq[i] is None:
+                    continue
+                c1[seq[i]] += 1
+                for k in range(2, order + 1):                                 # the k-gram that ends here, while it stays inside the line and its words are spelled
+                    if i - k + 1 < 0 or seq[i - k + 1] is None:
+                        break
+                    g = tuple(seq[i - k + 1:i + 1])
+                    counts[k][g] = counts[k].get(g, 0) + 1
+        p1 = (c1 + add_k) / (c1.sum() + add_k * max(n, 1))
+        P, BO = {}, {}                                                       # P[k]: the seen k-grams, BO[k]: ln backoff of the seen contexts of k words
+
+        def prob(k, h, w):
+            """P(w | the k - 1 words h) through level k and below"""
+            if k == 1:
+                return p1[w]
+            if h in P[k] and w in P[k][h]:
+                return P[k][h][w]
+            return float(np.exp(BO[k - 1].get(h, 0.0))) * prob(k - 1, h[1:], w)
+        for k in range(2, order + 1):
+            P[k], BO[k - 1] = _discounted(counts[k], lambda h, w, k=k: prob(k - 1, h[1:], w), n, discount)
+        BO[order] = {}
+        grams = {(w,): (float(np.log(p1[w])), BO[1].get((w,), 0.0)) for w in range(n)}
+        grams[(n,)] = (-99.0 * _LN10, BO[1].get((n,), 0.0))
+        for k in range(2, order + 1):
+            grams.update({h + (w,): (float(np.log(p)), BO[k].get(h + (w,), 0.0)) for h, ps in P[k].items() for w, p in ps.items()})
+        return cls(words, grams, chars, order, min_slots)
+
+    def write_arpa(self, path):
+        """ARPA text of the model (log10 values; the words as their cleaned spellings), readable by from_arpa and by other n-gram tools."""
+        name = self.words + ['<s>']
+        by = {}
+        for g in sorted(self.ngrams):
+            by.setdefault(len(g), []).append(g)
+        with open(path, 'w') as f:
+            f.write('\\data\\\n' + ''.join('ngram %d=%d\n' % (k, len(by[k])) for k in sorted(by)))
+            for k in sorted(by):
+                f.write('\n\\%d-grams:\n' % k)
+                for g in by[k]:
+                    lp, bo = self.ngrams[g]
+                    f.write('%.9g\t%s' % (float(lp) / _LN10, ' '.join(name[w] for w in g)) + ('\t%.9g\n' % (float(bo) / _LN10) if k < self._order else '\n'))
+            f.write('\n\\end\\\n')
+
+    def save(self, path):
+        by = {}
+        for g in sorted(self.ngrams):
+            by.setdefault(len(g), []).append(g)
+        arrays = {}
+        for k, gs in by.items():
+            arrays['ids_%d' % k] = np.asarray(gs, dtype=np.int32).reshape(len(gs), k)
+            arrays['val_%d' % k] = np.asarray([self.ngrams[g] for g in gs], dtype=np.float32).reshape(len(gs), 2)
+        with open(path, 'wb') as f:
+            np.savez(f, words=np.asarray(self.words, dtype=np.str_), chars=np.asarray(self.chars), order=np.asarray(self._order),
+                     min_slots=np.asarray(self.min_slots), **arrays)
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path) as z:
+            grams = {}
+            for k in range(1, cls.MAX_ORDER + 1):
+                if 'ids_%d' % k in z:
+                    grams.update({tuple(g): tuple(v) for g, v in zip(z['ids_%d' % k].tolist(), z['val_%d' % k])})
+            return cls([str(w) for w in z['words']], grams, str(z['chars']), int(z['order']), int(z['min_slots']))
+
+
 def _beam_search(head, V, blank, first, frames, beam_width, n_best, lm, alpha, beta, space=None):
     """One table upload, lse + search launches, one read-back.  head: (M, ld) f32 on the device; first / frames: per utterance, host ints.
-    A WordNgramLM selects the lexicon-constrained search (space: the class that ends a word, default V - 2)."""
+    A WordNgramLM or a WordStateLM selects the lexicon-constrained search of its kernel (space: the class that ends a word, default V - 2)."""
     n = len(frames)
     if n == 0:
         return []
@@ -523,6 +793,14 @@ def _beam_search(head, V, blank, first, frames, beam_width, n_best, lm, alpha, b
         labels, lengths, scores, _, _ = torch.ops.silent_speech.ctc_word_beam_search(
             head, utt, V, blank, space, int(sum(frames)), max_len, int(beam_width), int(n_best), lm.lex_child, lm.lex_word, lm.uni, lm.bi_keys, lm.bi_val,
             lm.tri_keys, lm.tri_val, lm.n_words, lm.start, lm.bi_probe, lm.tri_probe, float(alpha), float(beta))
+    elif isinstance(lm, WordStateLM):
+        if len(lm.chars) != V - 1:
+            raise ValueError('beam search: the WordStateLM spells with %d labels, the logits have %d classes' % (len(lm.chars), V))
+        space = V - 2 if space is None else int(space)
+        lm = lm.to(head.device)
+        labels, lengths, scores, _, _ = torch.ops.silent_speech.ctc_word_state_beam_search(
+            head, utt, V, blank, space, int(sum(frames)), max_len, int(beam_width), int(n_best), lm.lex_child, lm.lex_word, lm.uni_logp, lm.st_bo, lm.st_shorter,
+            lm.arc_keys, lm.arc_logp, lm.arc_next, lm.n_words, lm.start_state, lm.arc_probe, lm.order, float(alpha), float(beta))
     else:
         if lm is not None:
             lm = (lm.table if isinstance(lm, LabelNgramLM) else torch.as_tensor(lm, dtype=torch.float32)).to(head.device).contiguous()
@@ -538,7 +816,7 @@ def _beam_search(head, V, blank, first, frames, beam_width, n_best, lm, alpha, b
 
 def beam_decode(pred, lengths, blank=None, *, beam_width=100, n_best=1, lm=None, alpha=0.0, beta=0.0, space=None):
     """CTC prefix beam search of packed logits (rows, T, V) (NOT log-softmaxed), utterances back to back with `lengths` frames each, in one
-    launch on the device; lm: a LabelNgramLM (or its table) fused as alpha * ln P(label | two labels before) + beta per label, or a WordNgramLM:
+    launch on the device; lm: a LabelNgramLM (or its table) fused as alpha * ln P(label | two labels before) + beta per label, or a WordNgramLM / WordStateLM:
     the search is then confined to the spellings of its vocabulary and adds alpha * ln P(word | two words before) + beta per word; space = the
     class that ends a word (default V - 2, where TextTransform puts it; pass text_transform.chars.index(' ')).
     Returns a list of int lists, or for n_best > 1 a list of [(ints, score), ...] lists, best first (fewer than n_best if fewer prefixes exist;
@@ -688,7 +966,7 @@ def test(model, testset, device, *, batch_size=1, whole_utterances=False, decode
     plan call per group, every utterance computed as it is alone) and one arg-max launch + one read-back per group: the function of the
     default, at batched speed.
     decoder='greedy' (default): best-path decoding.  decoder='beam': the prefix beam search of beam_decode / beam_decode_utterances with
-    beam_width, and lm / alpha / beta if a LabelNgramLM or a WordNgramLM is given, in all three branches.  With a WordNgramLM (the reference's
+    beam_width, and lm / alpha / beta if a LabelNgramLM, a WordNgramLM or a WordStateLM is given, in all three branches.  With a word model (the reference's
     setting is alpha=1.5, beta=1.85) every predicted word is a word of its lexicon; ONE language model at a time: a LabelNgramLM and a
     WordNgramLM together (lm given as a list or tuple) raise ValueError."""
     if decoder not in ('greedy', 'beam'):
@@ -699,9 +977,9 @@ def test(model, testset, device, *, batch_size=1, whole_utterances=False, decode
     tt = testset.text_transform
     blank = len(tt.chars)
     if decoder == 'beam':
-        lm = lm.to(device) if isinstance(lm, (LabelNgramLM, WordNgramLM)) else lm   # the tables cross to the device once, not per utterance
+        lm = lm.to(device) if isinstance(lm, (LabelNgramLM, WordNgramLM, WordStateLM)) else lm   # the tables cross to the device once, not per utterance
         search = dict(beam_width=beam_width, lm=lm, alpha=alpha, beta=beta)
-        if isinstance(lm, WordNgramLM):
+        if isinstance(lm, (WordNgramLM, WordStateLM)):
             search['space'] = tt.chars.index(' ')
         decode = lambda pred, lengths: beam_decode(pred, lengths, blank, **search)
         decode_utterances = lambda logits: beam_decode_utterances(logits, **search)

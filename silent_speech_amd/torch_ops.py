@@ -9,6 +9,8 @@
     ctc_word_beam_search             the same search confined to a lexicon, a word n-gram with backoff scored at every word end (WordNgramLM), inference only
     ctc_forced_align                 best alignment of known label strings to the frame posteriors (CTC or blank-free linear topology), frame labels and token spans, one launch per batch (inference only)
     word_ngram_score                 ln P(w | w2, w1) of word triples by the device function of that search (tests, n-best rescoring)
+    ctc_word_state_beam_search       the lexicon-constrained search with a word n-gram of any order up to 6 held as context states (WordStateLM), inference only
+    word_state_score                 ln P(word | state) and the state after it by the device function of that search (tests, n-best rescoring)
     stft_logmel / stft_logmel_backward                 data_utils.py:39-62 and its gradient with respect to the audio (csrc/mel_bwd.hip)
     stft_logmel_ragged / stft_logmel_ragged_backward   the same pair for a ragged batch in one flat buffer (load_audio's clip included)
     emg_features                     data_utils.py:85-136 (get_emg_features; no autograd: the reference's features are numpy)
@@ -439,6 +441,92 @@ def _(triples, uni, bi_keys, bi_val, tri_keys, tri_val, bi_probe, tri_probe):
     return triples.new_empty((triples.shape[0],), dtype=torch.float32)
 
 
+# ------------------------------------------------------------------------------------------------ ctc_word_state_beam_search / word_state_score (inference only)
+def _word_state_tables(name, dev, uni_logp, st_bo, st_shorter, arc_keys, arc_logp, arc_next, arc_probe, order):
+    """Checks the tables of a WordStateLM (ss_word_state_lm in include/silent_speech_hip.h) and fills the part of the struct they make up."""
+    def bad(t, dtype):
+        return t.dtype != dtype or t.dim() != 1 or not t.is_contiguous() or t.device != dev
+    if not (1 <= order <= 6):
+        raise RuntimeError('%s: order %d (1 .. 6)' % (name, order))
+    if bad(uni_logp, torch.float32) or not (1 <= uni_logp.shape[0] <= 1 << 21):
+        raise RuntimeError('%s: the unigram table must be a contiguous (n <= 2^21) float32 tensor on the device of the input' % name)
+    n_uni = uni_logp.shape[0]
+    if bad(st_bo, torch.float32) or bad(st_shorter, torch.int32) or st_bo.shape[0] != st_shorter.shape[0] or st_bo.shape[0] < n_uni + 1 or st_bo.shape[0] >= 1 << 31:
+        raise RuntimeError('%s: the state tables must be float32 backoffs and int32 suffix links of one length >= %d (the empty context and one state per word id) '
+                           'on the device of the input' % (name, n_uni + 1))
+    slots = arc_keys.shape[0] if arc_keys.dim() == 1 else -1
+    if bad(arc_keys, torch.int64) or bad(arc_logp, torch.float32) or bad(arc_next, torch.int32) or arc_logp.shape[0] != slots or arc_next.shape[0] != slots or \
+            slots & (slots - 1) or not (0 <= arc_probe <= slots):
+        raise RuntimeError('%s: the arc table must be int64 keys, float32 values and int32 next states (slots) on the device of the input, '
+                           'slots 0 or a power of two, longest probe within them' % name)
+    lm = _lib.WordStateLm()
+    lm.uni_logp, lm.st_bo, lm.st_shorter = uni_logp.data_ptr(), st_bo.data_ptr(), st_shorter.data_ptr()
+    lm.arc_keys, lm.arc_logp, lm.arc_next = (arc_keys.data_ptr(), arc_logp.data_ptr(), arc_next.data_ptr()) if slots else (None, None, None)
+    lm.n_uni, lm.n_vocab, lm.n_states, lm.start_state, lm.n_nodes = n_uni, n_uni, st_bo.shape[0], 0, 0
+    lm.arc_slots, lm.arc_probe, lm.order = slots, arc_probe, order
+    _p(uni_logp)                                                         # (the one place that refuses memory the kernels cannot read)
+    return lm
+
+
+@torch.library.custom_op('silent_speech::ctc_word_state_beam_search', mutates_args=())
+def ctc_word_state_beam_search(logits: Tensor, utt: Tensor, V: int, blank: int, space: int, total_frames: int, max_len: int, beam_width: int, n_best: int,
+                               lex_child: Tensor, lex_word: Tensor, uni_logp: Tensor, st_bo: Tensor, st_shorter: Tensor, arc_keys: Tensor, arc_logp: Tensor,
+                               arc_next: Tensor, n_vocab: int, start_state: int, arc_probe: int, order: int, alpha: float,
+                               beta: float) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """ctc_word_beam_search with a word n-gram of any order 1 .. 6 held as context states (ss_ctc_word_state_beam_search in
+    include/silent_speech_hip.h).  logits .. n_best, lex_child, lex_word as for ctc_word_beam_search.  The tables are the device form of
+    recognition_model.WordStateLM: uni_logp [n_uni] f32, st_bo [n_states] f32 + st_shorter [n_states] int32, arc_keys [slots] int64 + arc_logp
+    [slots] f32 + arc_next [slots] int32, the word ids 0 .. n_vocab - 1 of the lexicon, the state of the start context, the longest probe sequence
+    of the arc table and the order.  Returns (labels, lengths, scores, CTC scores, complete) as ctc_word_beam_search."""
+    dev = logits.device
+    _beam_search_checks('ctc_word_state_beam_search', 2, logits, utt, V, blank, total_frames, max_len, beam_width, n_best)
+    if not (0 <= space < V) or space == blank:
+        raise RuntimeError('ctc_word_state_beam_search: space class %d (0 .. %d, not the blank %d)' % (space, V - 1, blank))
+    if lex_child.dim() != 2 or lex_child.shape[0] < 1 or lex_child.shape[1] != V - 1 or lex_child.dtype != torch.int32 or not lex_child.is_contiguous() or \
+            lex_child.device != dev or tuple(lex_word.shape) != (lex_child.shape[0],) or lex_word.dtype != torch.int32 or not lex_word.is_contiguous() or lex_word.device != dev:
+        raise RuntimeError('ctc_word_state_beam_search: the lexicon must be contiguous int32 tensors (n_nodes >= 1, %d) and (n_nodes) on the device of the logits' % (V - 1))
+    lm = _word_state_tables('ctc_word_state_beam_search', dev, uni_logp, st_bo, st_shorter, arc_keys, arc_logp, arc_next, arc_probe, order)
+    if not (0 <= n_vocab <= lm.n_uni) or not (0 <= start_state < lm.n_states):
+        raise RuntimeError('ctc_word_state_beam_search: %d words of %d word ids, start state %d of %d states' % (n_vocab, lm.n_uni, start_state, lm.n_states))
+    lm.lex_child, lm.lex_word, lm.n_nodes, lm.n_vocab, lm.start_state = lex_child.data_ptr(), lex_word.data_ptr(), lex_child.shape[0], n_vocab, start_state
+    lse, ws, st, out = _beam_search_buffers('ctc_word_state_beam_search', logits, utt, V, total_frames, max_len, beam_width, n_best,
+                                            _L().ss_ctc_word_state_beam_workspace_bytes)
+    n = utt.shape[0]
+    complete = torch.empty((n, n_best), dtype=torch.int32, device=dev)
+    _lib.check(_L().ss_ctc_word_state_beam_search(_p(logits), logits.shape[1], V, blank, space, logits.shape[0], _p(lse), _p(utt) if n else None, n, total_frames,
+                                                  beam_width, n_best, ctypes.byref(lm), alpha, beta, _p(ws), max_len, *(_p(t) for t in out), _p(complete), st),
+               'ss_ctc_word_state_beam_search')
+    return out + (complete,)
+
+
+@ctc_word_state_beam_search.register_fake
+def _(logits, utt, V, blank, space, total_frames, max_len, beam_width, n_best, lex_child, lex_word, uni_logp, st_bo, st_shorter, arc_keys, arc_logp, arc_next,
+      n_vocab, start_state, arc_probe, order, alpha, beta):
+    n = utt.shape[0]
+    return (logits.new_empty((n, n_best, max_len), dtype=torch.int32), logits.new_empty((n, n_best), dtype=torch.int32),
+            logits.new_empty((n, n_best)), logits.new_empty((n, n_best)), logits.new_empty((n, n_best), dtype=torch.int32))
+
+
+@torch.library.custom_op('silent_speech::word_state_score', mutates_args=())
+def word_state_score(pairs: Tensor, uni_logp: Tensor, st_bo: Tensor, st_shorter: Tensor, arc_keys: Tensor, arc_logp: Tensor, arc_next: Tensor,
+                     arc_probe: int, order: int) -> Tuple[Tensor, Tensor]:
+    """ln P(word | state) and the state after the word of every row (state, word) of pairs [n][2] int32 by the rule of ss_word_state_lm, with the
+    device function the word-state beam search uses.  An id outside the tables gives NaN and -1.  Returns ([n] f32, [n] int32)."""
+    dev = pairs.device
+    if pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.dtype != torch.int32 or not pairs.is_contiguous():
+        raise RuntimeError('word_state_score: pairs must be a contiguous (n, 2) int32 tensor')
+    lm = _word_state_tables('word_state_score', dev, uni_logp, st_bo, st_shorter, arc_keys, arc_logp, arc_next, arc_probe, order)
+    lnp = torch.empty(pairs.shape[0], dtype=torch.float32, device=dev)
+    nxt = torch.empty(pairs.shape[0], dtype=torch.int32, device=dev)
+    _lib.check(_L().ss_word_state_score(ctypes.byref(lm), _p(pairs), pairs.shape[0], _p(lnp), _p(nxt), _lib.stream_of(pairs)), 'ss_word_state_score')
+    return lnp, nxt
+
+
+@word_state_score.register_fake
+def _(pairs, uni_logp, st_bo, st_shorter, arc_keys, arc_logp, arc_next, arc_probe, order):
+    return pairs.new_empty((pairs.shape[0],), dtype=torch.float32), pairs.new_empty((pairs.shape[0],), dtype=torch.int32)
+
+
 # ------------------------------------------------------------------------------------------------ stft_logmel
 @torch.library.custom_op('silent_speech::stft_logmel', mutates_args=())
 def stft_logmel(y: Tensor, n_fft: int, num_mels: int, sampling_rate: int, hop_size: int, win_size: int, fmin: int, fmax: int, center: bool) -> Tensor:
@@ -769,6 +857,6 @@ def _(x, w, k, slope):
     return x.new_empty((x.shape[0],))
 
 
-OPS = ('model_forward', 'model_forward_ragged', 'model_backward', 'dtw_loss', 'dtw_align', 'ctc_loss', 'ctc_beam_search', 'ctc_word_beam_search', 'ctc_forced_align', 'word_ngram_score', 'stft_logmel', 'stft_logmel_backward', 'stft_logmel_ragged', 'stft_logmel_ragged_backward',
+OPS = ('model_forward', 'model_forward_ragged', 'model_backward', 'dtw_loss', 'dtw_align', 'ctc_loss', 'ctc_beam_search', 'ctc_word_beam_search', 'ctc_word_state_beam_search', 'ctc_forced_align', 'word_ngram_score', 'word_state_score', 'stft_logmel', 'stft_logmel_backward', 'stft_logmel_ragged', 'stft_logmel_ragged_backward',
        'emg_features', 'audio_resample', 'audio_level', 'spectral_gate_profile', 'spectral_gate', 'spectral_gate_nonstationary', 'fused_adamw',
        'vocoder_conv1d', 'vocoder_conv_transpose1d', 'vocoder_tail')
