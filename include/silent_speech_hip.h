@@ -30,9 +30,9 @@ extern "C" {
 const char* ss_last_error(void);
 /* Library/ABI version and the GPU architecture the kernels were compiled for ("gfx950"). */
 /* Bumped whenever a struct layout or an entry-point signature changes (3: ss_gemm_epilogue column-statistics fields, the plan /
- * attention-image / LayerNorm-workspace entry points, ss_dtw_cumulative; 4: ss_loss_index_tables; 5: gate recomputation arguments of ss_bn_backward_sums / ss_bn_backward_apply; 7: ss_split_planes / ss_gemm_planes, ss_dw_job.flags, up to 24 jobs per grouped launch; 8: ss_stft_logmel_fft, the rejected-frame counter behind the matrix of ss_phoneme_confusion; 9: planes_hi / planes_lo / planes_only of ss_gemm_epilogue, dropout groups of the GEMM epilogue are row-major; 10: ss_emg_features_batch; 11: the ss_voc_* vocoder entry points; 12: the ragged-batch inference entry points ss_bn_apply_ragged, ss_relpos_attention_forward_ragged, ss_plan_forward_ragged; 13: ss_ctc_beam_search / ss_ctc_beam_workspace_bytes; 14: ss_word_lm, ss_ctc_word_beam_search / ss_ctc_word_beam_workspace_bytes, ss_word_ngram_score; 15: ss_audio_resample_batch / ss_audio_resample_supported / ss_audio_resample_limits, ss_audio_level_batch; 16: ss_spectral_gate_profile / ss_spectral_gate_batch / ss_spectral_gate_limits; 17: ss_stft_logmel_fft_backward / ss_stft_logmel_fft_backward_workspace_bytes; 18: ss_ctc_align / ss_ctc_align_workspace_bytes; 19: ss_spectral_gate_ns_batch; 20: ss_iir_filtfilt / ss_iir_filtfilt_workspace_bytes / ss_linear_resample / ss_reflect_pad removed, a single signal is a batch of one; 21: ss_word_state_lm, ss_ctc_word_state_beam_search / ss_ctc_word_state_beam_workspace_bytes, ss_word_state_score).  Bindings must compare it with SS_ABI_VERSION at load time: a stale
+ * attention-image / LayerNorm-workspace entry points, ss_dtw_cumulative; 4: ss_loss_index_tables; 5: gate recomputation arguments of ss_bn_backward_sums / ss_bn_backward_apply; 7: ss_split_planes / ss_gemm_planes, ss_dw_job.flags, up to 24 jobs per grouped launch; 8: ss_stft_logmel_fft, the rejected-frame counter behind the matrix of ss_phoneme_confusion; 9: planes_hi / planes_lo / planes_only of ss_gemm_epilogue, dropout groups of the GEMM epilogue are row-major; 10: ss_emg_features_batch; 11: the ss_voc_* vocoder entry points; 12: the ragged-batch inference entry points ss_bn_apply_ragged, ss_relpos_attention_forward_ragged, ss_plan_forward_ragged; 13: ss_ctc_beam_search / ss_ctc_beam_workspace_bytes; 14: ss_word_lm, ss_ctc_word_beam_search / ss_ctc_word_beam_workspace_bytes, ss_word_ngram_score; 15: ss_audio_resample_batch / ss_audio_resample_supported / ss_audio_resample_limits, ss_audio_level_batch; 16: ss_spectral_gate_profile / ss_spectral_gate_batch / ss_spectral_gate_limits; 17: ss_stft_logmel_fft_backward / ss_stft_logmel_fft_backward_workspace_bytes; 18: ss_ctc_align / ss_ctc_align_workspace_bytes; 19: ss_spectral_gate_ns_batch; 20: ss_iir_filtfilt / ss_iir_filtfilt_workspace_bytes / ss_linear_resample / ss_reflect_pad removed, a single signal is a batch of one; 21: ss_word_state_lm, ss_ctc_word_state_beam_search / ss_ctc_word_state_beam_workspace_bytes, ss_word_state_score; 22: ss_edit_distance / ss_edit_distance_workspace_bytes, ss_nbest_risk).  Bindings must compare it with SS_ABI_VERSION at load time: a stale
  * library paired with newer headers would otherwise read garbage struct fields instead of failing. */
-#define SS_ABI_VERSION 21
+#define SS_ABI_VERSION 22
 int ss_abi_version(void);
 const char* ss_target_arch(void);
 
@@ -503,6 +503,42 @@ int64_t ss_ctc_align_workspace_bytes(int n_utt, int64_t total_frames, int max_ta
 int ss_ctc_align(const float* logits, int64_t ld, int V, int blank, int64_t rows, const float* lse, const int64_t* utt_dev, int n_utt,
                  int64_t total_frames, int max_target_len, const int32_t* targets, int64_t n_targets, void* workspace, float* score,
                  int32_t* frame_token, int32_t* token_first, int32_t* token_frames, float* token_logp, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Scoring transcripts: the Levenshtein distance of token strings with its error breakdown and alignment, a batch of pairs in one launch, and the
+ * minimum-Bayes-risk pass over n-best lists (csrc/edit_distance.hip; what jiwer / rapidfuzz compute for one pair on the host).
+ * Inputs: tokens (n_tokens) int32, flat; seqs (device, int64 x2 per sequence) = first token, length; pairs (device, int32 x2 per pair) =
+ * reference sequence a, hypothesis sequence b.  Tokens are compared by ==.  A sequence has at most 1023 tokens.
+ * Definition: D[0][j] = j, D[i][0] = i, D[i][j] = min(D[i-1][j-1] + (a[i-1] != b[j-1]), D[i-1][j] + 1, D[i][j-1] + 1), distance = D[n_a][n_b].
+ *   ties: the predecessor of a cell is the FIRST of {diagonal, up (a reference token is deleted), left (a hypothesis token is inserted)} that
+ *     attains the minimum; in row 0 it is left, in column 0 up.  (hits, substitutions, deletions, insertions) are the counts of the path these
+ *     predecessors define from (n_a, n_b) back to (0, 0): hits + S + D = n_a, hits + S + I = n_b, S + D + I = distance.  The kernel carries the
+ *     counts forward with the distance -- the chosen predecessor is the same cell either way -- so the counts need no backtrace.
+ *   Parity with the tie choice of jiwer / rapidfuzz (which of several alignments of least cost they report) is UNPINNED, as parity with ctcdecode
+ *     is: neither is available to compare against.  The distance itself, and with it WER / CER, does not depend on the ties.
+ * Outputs: dist (n_pairs) int32; counts (n_pairs, 4) int32 = hits, substitutions, deletions, insertions.
+ * Alignment (ops_first != NULL): ops_first (device, n_pairs + 1 int64, non-decreasing) gives pair p the bytes [ops_first[p], ops_first[p + 1]) of
+ *   ops (n_ops int8), at least n_a + n_b of them: one byte per step of the path FROM THE BEGINNING, 0 hit, 1 substitution, 2 deletion, 3
+ *   insertion, then -1 to the end of the pair's bytes; bytes of no pair are not written.  workspace: ss_edit_distance_workspace_bytes(n_pairs,
+ *   n_ops) bytes (2-bit back-pointers; needs no initialisation); -1 = bad arguments.  ops_first = NULL: distance and counts only, no workspace.
+ * Bad table entries are cut short, never read out of bounds: a pair with a sequence index outside [0, n_seq), a negative length, a length above
+ *   1023, a span that leaves [0, n_tokens), or (alignment) bytes that leave [0, n_ops) or are fewer than n_a + n_b gets dist = -1, counts = -1
+ *   and -1 in whatever of its ops bytes lie inside ops; every other pair is unaffected.  n_pairs = 0 launches nothing. */
+int64_t ss_edit_distance_workspace_bytes(int64_t n_pairs, int64_t n_ops);
+int ss_edit_distance(const int32_t* tokens, int64_t n_tokens, const int64_t* seqs, int64_t n_seq, const int32_t* pairs, int64_t n_pairs,
+                     int32_t* dist, int32_t* counts, int8_t* ops, const int64_t* ops_first, int64_t n_ops, void* workspace, void* stream);
+/* Minimum-Bayes-risk selection from n-best lists, two launches.  tokens, seqs as above; groups (device, int64 x2 per group) = first sequence, K:
+ * the 1 <= K <= max_k <= 128 consecutive sequences of one list in rank order (groups should not share sequences); weights (n_seq) f32, the
+ * posterior of every sequence within its list.
+ * dmat (n_dmat int32): group g's K x K matrix of distances (the definition above; symmetric, every unordered pair computed once, diagonal 0),
+ *   row-major at the sum of K_h^2 over h < g.  risk (n_seq) f64, parallel to weights: risk[first + i] = sum_k weights[first + k] * dmat[i][k],
+ *   accumulated in f64 in ascending k (an f32 times an integer below 2^11 is exact in f64, so the value depends on the order alone).
+ *   pick (n_groups) int32 = the smallest i of least risk.
+ * Bad table entries: a K outside 1 .. 128 takes no room in dmat and gives pick -1; a group whose sequences leave [0, n_seq) or whose matrix
+ *   leaves [0, n_dmat), a bad sequence in a group (its row and column of dmat are -1) or a NaN risk give pick -1 and NaN risks for the
+ *   sequences of the group that exist.  Entries of risk outside every group are not written.  n_groups = 0 launches nothing. */
+int ss_nbest_risk(const int32_t* tokens, int64_t n_tokens, const int64_t* seqs, int64_t n_seq, const int64_t* groups, int n_groups, int max_k,
+                  const float* weights, int32_t* dmat, int64_t n_dmat, double* risk, int32_t* pick, void* stream);
 
 /* AdamW over a flat f32 arena (transduction_model.py:178,210).  step is 1-based. */
 int ss_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,

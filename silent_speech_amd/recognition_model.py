@@ -12,7 +12,11 @@
     forced_align(logits, lengths, targets)   best alignment of KNOWN label strings to the frames on the device (csrc/ctc_align.hip): Alignment per
                                              utterance; forced_align_utterances for the list Model.forward_utterances returns
     word_segments(alignment, text_int, tt)   (word, start_s, end_s, confidence) of a character alignment; align(model, testset, device) for a data set
-    test(model, testset, device)             :30-58 -> WER; decoder='greedy' (default) or 'beam'
+    edit_distance(references, hypotheses)    Levenshtein distance with hits / substitutions / deletions / insertions and the alignment, a batch of
+                                             pairs in one launch (csrc/edit_distance.hip); word_errors / cer: the jiwer measures of transcripts
+    mbr_rerank(nbest, space=..)              minimum-Bayes-risk choice from n-best lists (all K^2 word distances per list on the device);
+                                             oracle_errors: the best hypothesis of every list against its reference
+    test(model, testset, device)             :30-58 -> WER; decoder='greedy' (default) or 'beam'; mbr=K, details=True
     train_model(trainset, devset, device)    :61-117 (AdamW, warm-up, x2 gradient accumulation, MultiStepLR)
 
 The encoder is the same MI355X engine as the transduction trainer (Model without the aux head).  The CTC
@@ -23,7 +27,9 @@ in one launch, with shallow fusion of a label n-gram table that lives on the dev
 KenLM model -- confined to the spellings of a vocabulary with a WORD n-gram with backoff scored at every word end (WordNgramLM: orders 1 to 3 as
 hashed n-gram keys; WordStateLM: orders 1 to 6 as KenLM-style context states; both read from ARPA text or counted from transcripts; the search is lexicon-constrained, there is no out-of-vocabulary escape).  Out of scope: the
 KenLM BINARY format (third-party C++; convert lm.binary to ARPA text) and parity with ctcdecode's own numbers, which stays unpinned because
-ctcdecode is not available to compare against.  test() reports greedy WER by default and beam-search WER with decoder='beam'.
+ctcdecode is not available to compare against.  The same holds for the scoring (edit_distance, word_errors, mbr_rerank on csrc/edit_distance.hip):
+WER and CER do not depend on it, but which of several alignments of equal cost jiwer / rapidfuzz report -- and with it their split into
+substitutions, deletions and insertions in a tie -- is unpinned; the header states the tie rule used here.  test() reports greedy WER by default and beam-search WER with decoder='beam'.
 """
 import collections
 import logging
@@ -142,6 +148,188 @@ def wer(references, predictions):
     errs = sum(_edit_distance(r.split(), p.split()) for r, p in zip(references, predictions))
     words = sum(len(r.split()) for r in references)
     return errs / max(words, 1)
+
+
+EditResult = collections.namedtuple('EditResult', ['distance', 'hits', 'substitutions', 'deletions', 'insertions', 'ops'])
+EditResult.__doc__ = """Levenshtein distance of one (reference, hypothesis) pair with its breakdown (ss_edit_distance in include/silent_speech_hip.h states the
+definition and the tie rule): hits + substitutions + deletions = reference length, hits + substitutions + insertions = hypothesis length,
+substitutions + deletions + insertions = distance.  ops: the alignment as an int8 array, one entry per step from the beginning (0 hit, 1 substitution,
+2 deletion, 3 insertion), or None when it was not asked for."""
+ErrorCounts = collections.namedtuple('ErrorCounts', ['hits', 'substitutions', 'deletions', 'insertions', 'reference_tokens', 'rate', 'per_utterance'])
+ErrorCounts.__doc__ = """The measures jiwer reports for a test set: the four counts summed over the utterances, the number of reference tokens N,
+rate = (S + D + I) / max(N, 1) -- the WER for words, the CER for characters -- and the EditResult of every utterance."""
+MAX_EDIT_TOKENS = 1023
+MAX_NBEST = 128
+
+
+def _scoring_device(device):
+    if device is not None:
+        return torch.device(device)
+    return torch.device('cpu') if _lib.is_emulator() else torch.device('cuda')
+
+
+class _TokenTable(object):
+    """Sequences of hashable tokens as the flat int32 tokens and the (first token, length) table of ss_edit_distance; ids are interned per table."""
+
+    def __init__(self, who):
+        self.who, self.ids, self.flat, self.rows = who, {}, [], []
+
+    def add(self, seq):
+        seq = list(seq)
+        if len(seq) > MAX_EDIT_TOKENS:
+            raise ValueError('%s: a sequence of %d tokens (at most %d)' % (self.who, len(seq), MAX_EDIT_TOKENS))
+        ids = self.ids
+        self.rows.append((len(self.flat), len(seq)))
+        self.flat.extend(ids.setdefault(t, len(ids)) for t in seq)
+        return len(self.rows) - 1
+
+    def arrays(self):
+        """(tokens with one spare entry: never an empty upload, seqs)"""
+        return np.asarray(self.flat + [0], dtype=np.int32), np.asarray(self.rows, dtype=np.int64).reshape(len(self.rows), 2)
+
+
+def _edit_results(table, pairs, ops, device):
+    """One upload, one launch, one read-back: the EditResult of every (reference row, hypothesis row) of `pairs` over the sequences of `table`."""
+    if not pairs:
+        return []
+    flat, seqs = table.arrays()
+    tokens, seqs_d, pairs_d = staging.upload([flat, seqs, np.asarray(pairs, dtype=np.int32).reshape(len(pairs), 2)], device)
+    dist, counts, ops_d, _ = torch.ops.silent_speech.edit_distance(tokens, seqs_d, pairs_d, bool(ops))
+    back = torch.cat([dist, counts.reshape(-1), ops_d.to(torch.int32)]).cpu().numpy()                  # ONE read-back
+    n = len(pairs)
+    dist, counts, steps = back[:n], back[n:5 * n].reshape(n, 4), back[5 * n:].astype(np.int8)
+    out, at = [], 0
+    for p, (a, b) in enumerate(pairs):
+        if dist[p] < 0:
+            raise RuntimeError('edit_distance: pair %d was refused by the kernel' % p)
+        path = None
+        if ops:
+            room, n_path = table.rows[a][1] + table.rows[b][1], int(counts[p].sum())
+            path, at = steps[at:at + n_path].copy(), at + room
+        out.append(EditResult(int(dist[p]), int(counts[p, 0]), int(counts[p, 1]), int(counts[p, 2]), int(counts[p, 3]), path))
+    return out
+
+
+def edit_distance(references, hypotheses, *, ops=False, device=None):
+    """Levenshtein distance with the jiwer breakdown of every (reference, hypothesis) pair, the whole batch in one launch on the device
+    (csrc/edit_distance.hip).  references / hypotheses: equally many token lists (ints or any hashables, compared by ==, at most 1023 each).
+    ops=True adds the alignment.  Returns a list of EditResult.  The tie rule among alignments of equal cost is the one the header states; parity
+    with jiwer's own choice is unpinned (jiwer is not available to compare against) -- the distance and the rates do not depend on it."""
+    references, hypotheses = list(references), list(hypotheses)
+    if len(references) != len(hypotheses):
+        raise ValueError('edit_distance: %d references for %d hypotheses' % (len(references), len(hypotheses)))
+    table = _TokenTable('edit_distance')
+    pairs = [(table.add(r), table.add(h)) for r, h in zip(references, hypotheses)]
+    return _edit_results(table, pairs, ops, _scoring_device(device))
+
+
+def _error_counts(results, n_ref):
+    h, s, d, i = (sum(r[k] for r in results) for k in (1, 2, 3, 4))
+    return ErrorCounts(h, s, d, i, n_ref, (s + d + i) / max(n_ref, 1), results)
+
+
+def _units(text, unit, who):
+    if unit == 'word':
+        return text.split()
+    if unit == 'char':
+        return list(text)
+    raise ValueError("%s: unit is 'word' or 'char'" % who)
+
+
+def word_errors(references, predictions, *, unit='word', device=None):
+    """What jiwer.compute_measures reports for transcripts: hits, substitutions, deletions and insertions over the words (unit='char': the
+    characters) of the reference strings against the predicted strings, one launch for the test set.  Returns ErrorCounts; its rate is the
+    value wer() returns for unit='word'."""
+    refs = [_units(r, unit, 'word_errors') for r in references]
+    hyps = [_units(p, unit, 'word_errors') for p in predictions]
+    return _error_counts(edit_distance(refs, hyps, device=device), sum(len(r) for r in refs))
+
+
+def cer(references, predictions, *, device=None):
+    """Character error rate: total character edit distance / total reference characters."""
+    return word_errors(references, predictions, unit='char', device=device).rate
+
+
+def _label_units(ints, space, unit, who):
+    """The scoring tokens of a label string: unit='word' the runs of labels between `space` labels (as tuples), unit='char' the labels."""
+    ints = [int(c) for c in ints]
+    if unit == 'char':
+        return ints
+    if unit != 'word':
+        raise ValueError("%s: unit is 'word' or 'char'" % who)
+    words, run = [], []
+    for c in ints + [space]:
+        if c != space:
+            run.append(c)
+        elif run:
+            words.append(tuple(run))
+            run = []
+    return words
+
+
+def mbr_rerank(nbest, *, space, scale=1.0, unit='word', device=None):
+    """Minimum-Bayes-risk selection from the n-best lists beam_decode*(.., n_best=K) return: per utterance the hypothesis of the least expected
+    word (unit='char': label) edit distance to the others under the list's own posterior, softmax(scale * score) over the list (f64 on the
+    host, rounded to f32).  Words are the runs of labels between `space` labels, interned across the batch.  All K^2 distances of every
+    list, the risks and the choice are computed on the device (ss_nbest_risk, two launches).  Returns per utterance (pick, risks): the index of the
+    chosen hypothesis (the better rank among equal risks; -1 for an empty list) and the f64 risk of every hypothesis.  At most 128 hypotheses
+    per utterance; an utterance with fewer than K is a smaller group."""
+    space = int(space)
+    table, groups, weights = _TokenTable('mbr_rerank'), [], []
+    for hyps in nbest:
+        hyps = list(hyps)
+        if len(hyps) > MAX_NBEST:
+            raise ValueError('mbr_rerank: %d hypotheses for one utterance (at most %d)' % (len(hyps), MAX_NBEST))
+        if hyps:
+            groups.append((len(table.rows), len(hyps)))
+            z = np.asarray([float(score) for _, score in hyps], dtype=np.float64) * float(scale)
+            z = np.exp(z - z.max())
+            weights.extend((z / z.sum()).astype(np.float32))
+        for ints, _ in hyps:
+            table.add(_label_units(ints, space, unit, 'mbr_rerank'))
+    out = [(-1, np.zeros(0, dtype=np.float64)) for _ in nbest]
+    if not groups:
+        return out
+    flat, seqs = table.arrays()
+    tokens, seqs_d, groups_d, weights_d = staging.upload([flat, seqs, np.asarray(groups, dtype=np.int64), np.asarray(weights, dtype=np.float32)],
+                                                         _scoring_device(device))
+    _, risk, pick = torch.ops.silent_speech.nbest_risk(tokens, seqs_d, groups_d, weights_d)
+    back = torch.cat([risk, pick.to(torch.float64)]).cpu().numpy()                                      # ONE read-back
+    risk, pick = back[:len(table.rows)], back[len(table.rows):].astype(np.int64)
+    g = 0
+    for u, hyps in enumerate(nbest):
+        if len(hyps):
+            first, K = groups[g]
+            if pick[g] < 0:
+                raise RuntimeError('mbr_rerank: utterance %d was refused by the kernel' % u)
+            out[u] = (int(pick[g]), risk[first:first + K].copy())
+            g += 1
+    return out
+
+
+def oracle_errors(references, nbest, *, space, unit='word', device=None):
+    """Oracle error rate of n-best lists: per utterance the hypothesis of the least word (unit='char': label) edit distance to the reference
+    (the better rank among equals), from ONE edit-distance launch over all (utterance, hypothesis) pairs.  references: one label string (ints,
+    the labels of the hypotheses) per utterance; nbest: what beam_decode*(.., n_best=K) returns.  An empty list counts as the empty hypothesis
+    (choice -1).  Returns (choices, ErrorCounts of the chosen hypotheses)."""
+    references, nbest = list(references), list(nbest)
+    if len(references) != len(nbest):
+        raise ValueError('oracle_errors: %d references for %d n-best lists' % (len(references), len(nbest)))
+    space = int(space)
+    table, pairs, spans, n_ref = _TokenTable('oracle_errors'), [], [], 0
+    for ref, hyps in zip(references, nbest):
+        r = table.add(_label_units(ref, space, unit, 'oracle_errors'))
+        n_ref += table.rows[r][1]
+        cand = [table.add(_label_units(ints, space, unit, 'oracle_errors')) for ints, _ in hyps] or [table.add([])]
+        spans.append((len(pairs), len(cand), len(hyps)))
+        pairs.extend((r, h) for h in cand)
+    results = _edit_results(table, pairs, False, _scoring_device(device))
+    choices, chosen = [], []
+    for first, n, n_hyps in spans:
+        best = min(range(n), key=lambda k: (results[first + k].distance, k))
+        choices.append(best if n_hyps else -1)
+        chosen.append(results[first + best])
+    return choices, _error_counts(chosen, n_ref)
 
 
 def greedy_decode_utterances(logits):
@@ -958,7 +1146,8 @@ def align(model, testset, device, *, batch_size=8):
     return out
 
 
-def test(model, testset, device, *, batch_size=1, whole_utterances=False, decoder='greedy', beam_width=100, lm=None, alpha=0.0, beta=0.0):
+def test(model, testset, device, *, batch_size=1, whole_utterances=False, decoder='greedy', beam_width=100, lm=None, alpha=0.0, beta=0.0,
+         mbr=None, mbr_scale=1.0, details=False):
     """:30-58.  Default (batch_size=1) = the reference: eval-mode forward of ONE WHOLE utterance at a time (:37-43), so the convolutions
     and the +-99-frame attention band span the utterance (the banded attention kernels take any T).  batch_size > 1 packs the utterances
     into 200-frame rows like training does -- faster, but context is cut at the row boundaries, so its WER is not the reference's number.
@@ -968,9 +1157,14 @@ def test(model, testset, device, *, batch_size=1, whole_utterances=False, decode
     decoder='greedy' (default): best-path decoding.  decoder='beam': the prefix beam search of beam_decode / beam_decode_utterances with
     beam_width, and lm / alpha / beta if a LabelNgramLM, a WordNgramLM or a WordStateLM is given, in all three branches.  With a word model (the reference's
     setting is alpha=1.5, beta=1.85) every predicted word is a word of its lexicon; ONE language model at a time: a LabelNgramLM and a
-    WordNgramLM together (lm given as a list or tuple) raise ValueError."""
+    WordNgramLM together (lm given as a list or tuple) raise ValueError.
+    mbr=K (with decoder='beam', 2 <= K <= 128): the search returns its K best and the scored prediction is their minimum-Bayes-risk choice under
+    softmax(mbr_scale * score) (mbr_rerank).  details=True: the ErrorCounts of word_errors (hits, substitutions, deletions, insertions, the
+    rate and every utterance's own counts) instead of the bare rate."""
     if decoder not in ('greedy', 'beam'):
         raise ValueError("test: decoder is 'greedy' or 'beam'")
+    if mbr is not None and (decoder != 'beam' or not (2 <= int(mbr) <= MAX_NBEST)):
+        raise ValueError("test: mbr=K needs decoder='beam' and 2 <= K <= %d" % MAX_NBEST)
     if isinstance(lm, (list, tuple)):
         raise ValueError('test: one language model at a time -- a LabelNgramLM and a WordNgramLM cannot be combined')
     model.eval()
@@ -981,8 +1175,17 @@ def test(model, testset, device, *, batch_size=1, whole_utterances=False, decode
         search = dict(beam_width=beam_width, lm=lm, alpha=alpha, beta=beta)
         if isinstance(lm, (WordNgramLM, WordStateLM)):
             search['space'] = tt.chars.index(' ')
-        decode = lambda pred, lengths: beam_decode(pred, lengths, blank, **search)
-        decode_utterances = lambda logits: beam_decode_utterances(logits, **search)
+        if mbr is not None:
+            search['n_best'] = int(mbr)
+            space = tt.chars.index(' ')
+
+            def choose(lists):
+                picks = mbr_rerank(lists, space=space, scale=mbr_scale, device=device)
+                return [hyps[pick][0] if pick >= 0 else [] for hyps, (pick, _) in zip(lists, picks)]
+        else:
+            choose = lambda ints: ints
+        decode = lambda pred, lengths: choose(beam_decode(pred, lengths, blank, **search))
+        decode_utterances = lambda logits: choose(beam_decode_utterances(logits, **search))
     else:
         decode = lambda pred, lengths: greedy_decode(pred, lengths, blank)
         decode_utterances = greedy_decode_utterances
@@ -1013,6 +1216,8 @@ def test(model, testset, device, *, batch_size=1, whole_utterances=False, decode
                     predictions.append(tt.int_to_text(ints))
                     references.append(tt.int_to_text(tgt.tolist()))
     model.train()
+    if details:
+        return word_errors(references, predictions, device=device)
     return wer(references, predictions)
 
 

@@ -8,6 +8,7 @@
     ctc_beam_search                  the search of recognition_model.py:33-35,48-49: CTC prefix beam search + label n-gram table, one launch per batch (inference only)
     ctc_word_beam_search             the same search confined to a lexicon, a word n-gram with backoff scored at every word end (WordNgramLM), inference only
     ctc_forced_align                 best alignment of known label strings to the frame posteriors (CTC or blank-free linear topology), frame labels and token spans, one launch per batch (inference only)
+    edit_distance / nbest_risk       Levenshtein distance with its error breakdown and alignment for a batch of pairs in one launch; all K^2 distances, risks and the MBR choice of n-best lists
     word_ngram_score                 ln P(w | w2, w1) of word triples by the device function of that search (tests, n-best rescoring)
     ctc_word_state_beam_search       the lexicon-constrained search with a word n-gram of any order up to 6 held as context states (WordStateLM), inference only
     word_state_score                 ln P(word | state) and the state after it by the device function of that search (tests, n-best rescoring)
@@ -421,6 +422,106 @@ def _(logits, utt, targets, V, blank, total_frames, max_target_len):
     n, nt = utt.shape[0], targets.shape[0]
     return (logits.new_empty((n,)), logits.new_empty((logits.shape[0],), dtype=torch.int32), logits.new_empty((nt,), dtype=torch.int32),
             logits.new_empty((nt,), dtype=torch.int32), logits.new_empty((nt,)))
+
+
+# ------------------------------------------------------------------------------------------------ edit_distance / nbest_risk (scoring: no autograd)
+MAX_EDIT_TOKENS = 1023
+MAX_NBEST = 128
+
+
+def _edit_tables(name, tokens, seqs):
+    dev = tokens.device
+    if tokens.dim() != 1 or tokens.dtype != torch.int32 or not tokens.is_contiguous():
+        raise RuntimeError('%s: tokens must be a contiguous flat int32 tensor' % name)
+    if seqs.dim() != 2 or seqs.shape[1] != 2 or seqs.dtype != torch.int64 or not seqs.is_contiguous() or seqs.device != dev:
+        raise RuntimeError('%s: seqs must be a contiguous (n, 2) int64 table (first token, length) on the device of the tokens' % name)
+
+
+@torch.library.custom_op('silent_speech::edit_distance', mutates_args=())
+def edit_distance(tokens: Tensor, seqs: Tensor, pairs: Tensor, want_ops: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """Levenshtein distance, error breakdown and (want_ops) alignment of a batch of pairs in one launch (ss_edit_distance in
+    include/silent_speech_hip.h states the definition and the ties).  tokens flat int32; seqs [n_seq][2] int64 = (first token, length <= 1023);
+    pairs [n][2] int32 = (reference sequence, hypothesis sequence).
+    Returns (dist [n] int32, counts [n][4] int32 = hits, substitutions, deletions, insertions, ops int8, ops_first [n + 1] int64): pair p's
+    alignment is ops[ops_first[p] : ops_first[p + 1]] (n_a + n_b bytes: 0 hit, 1 substitution, 2 deletion, 3 insertion from the beginning, then
+    -1); both are empty without want_ops.  A pair with a bad table entry gets -1s (and no ops bytes)."""
+    dev = tokens.device
+    _edit_tables('edit_distance', tokens, seqs)
+    if pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.dtype != torch.int32 or not pairs.is_contiguous() or pairs.device != dev:
+        raise RuntimeError('edit_distance: pairs must be a contiguous (n, 2) int32 table on the device of the tokens')
+    n, n_seq, n_tok = pairs.shape[0], seqs.shape[0], tokens.shape[0]
+    if n > 1 << 24:
+        raise RuntimeError('edit_distance: %d pairs (at most 2^24 in one launch)' % n)
+    dist = torch.empty(n, dtype=torch.int32, device=dev)
+    counts = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    ops = torch.empty(0, dtype=torch.int8, device=dev)
+    ops_first = torch.empty(0, dtype=torch.int64, device=dev)
+    ws = None
+    n_ops = 0
+    if want_ops:
+        # the room of every pair, from the tables where they lie: n_a + n_b of the entries that are in range, none for the others
+        ops_first = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        if n and n_seq:
+            ln = seqs[:, 1]
+            ln = torch.where((ln >= 0) & (ln <= MAX_EDIT_TOKENS), ln, torch.zeros_like(ln))
+            ix = pairs.to(torch.int64)
+            inside = ((ix >= 0) & (ix < n_seq)).all(1)
+            room = ln[ix.clamp(0, n_seq - 1)].sum(1) * inside
+            ops_first[1:] = torch.cumsum(room, 0)
+            n_ops = int(ops_first[-1])
+        ops = torch.empty(n_ops, dtype=torch.int8, device=dev)
+        ws_bytes = _L().ss_edit_distance_workspace_bytes(n, n_ops)
+        if ws_bytes < 0:
+            raise RuntimeError('edit_distance: %d pairs with %d alignment bytes' % (n, n_ops))
+        ws = torch.empty(max(ws_bytes // 4, 1), dtype=torch.int32, device=dev)
+    if n:
+        _lib.check(_L().ss_edit_distance(_p(tokens) if n_tok else None, n_tok, _p(seqs) if n_seq else None, n_seq, _p(pairs), n, _p(dist), _p(counts),
+                                         _p(ops) if n_ops else None, _p(ops_first) if want_ops else None, n_ops, _p(ws), _lib.stream_of(tokens)), 'ss_edit_distance')
+    return dist, counts, ops, ops_first
+
+
+@edit_distance.register_fake
+def _(tokens, seqs, pairs, want_ops):
+    n = pairs.shape[0]
+    n_ops = torch.library.get_ctx().new_dynamic_size() if want_ops else 0
+    return (tokens.new_empty((n,)), tokens.new_empty((n, 4)), tokens.new_empty((n_ops,), dtype=torch.int8),
+            tokens.new_empty((n + 1 if want_ops else 0,), dtype=torch.int64))
+
+
+@torch.library.custom_op('silent_speech::nbest_risk', mutates_args=())
+def nbest_risk(tokens: Tensor, seqs: Tensor, groups: Tensor, weights: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """Minimum-Bayes-risk selection from n-best lists (ss_nbest_risk in include/silent_speech_hip.h): tokens, seqs as for edit_distance; groups
+    [n_groups][2] int64 = (first sequence, K <= 128 consecutive sequences, rank order); weights [n_seq] f32, the posterior of every sequence
+    within its list.  Returns (dmat int32, group g's K x K distance matrix at the sum of the K^2 before it, risk [n_seq] f64 =
+    sum_k weights[k] dmat[i][k] in ascending k (NaN outside every group), pick [n_groups] int32 = the smallest index of least risk; -1 and NaN
+    risks for a group with a bad table entry).  The group sizes are read back once to size dmat."""
+    dev = tokens.device
+    _edit_tables('nbest_risk', tokens, seqs)
+    if groups.dim() != 2 or groups.shape[1] != 2 or groups.dtype != torch.int64 or not groups.is_contiguous() or groups.device != dev:
+        raise RuntimeError('nbest_risk: groups must be a contiguous (n, 2) int64 table (first sequence, K) on the device of the tokens')
+    n_seq, n_tok, ng = seqs.shape[0], tokens.shape[0], groups.shape[0]
+    if weights.dim() != 1 or weights.shape[0] != n_seq or weights.dtype != torch.float32 or not weights.is_contiguous() or weights.device != dev:
+        raise RuntimeError('nbest_risk: weights must be a contiguous (%d) float32 tensor on the device of the tokens' % n_seq)
+    if ng > 65535:
+        raise RuntimeError('nbest_risk: %d groups (at most 65535 in one call)' % ng)
+    K = groups[:, 1].cpu()
+    if ng and (int(K.min()) < 1 or int(K.max()) > MAX_NBEST):
+        raise RuntimeError('nbest_risk: groups of %d .. %d sequences (1 .. %d)' % (int(K.min()), int(K.max()), MAX_NBEST))
+    n_dmat = int((K * K).sum())
+    dmat = torch.empty(n_dmat, dtype=torch.int32, device=dev)
+    risk = torch.full((n_seq,), float('nan'), dtype=torch.float64, device=dev)
+    pick = torch.empty(ng, dtype=torch.int32, device=dev)
+    if ng:
+        _lib.check(_L().ss_nbest_risk(_p(tokens) if n_tok else None, n_tok, _p(seqs) if n_seq else None, n_seq, _p(groups), ng, int(K.max()),
+                                      _p(weights) if n_seq else None, _p(dmat) if n_dmat else None, n_dmat, _p(risk) if n_seq else None, _p(pick),
+                                      _lib.stream_of(tokens)), 'ss_nbest_risk')
+    return dmat, risk, pick
+
+
+@nbest_risk.register_fake
+def _(tokens, seqs, groups, weights):
+    return (tokens.new_empty((torch.library.get_ctx().new_dynamic_size(),)), tokens.new_empty((seqs.shape[0],), dtype=torch.float64),
+            tokens.new_empty((groups.shape[0],)))
 
 
 @torch.library.custom_op('silent_speech::word_ngram_score', mutates_args=())
