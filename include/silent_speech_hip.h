@@ -30,9 +30,9 @@ extern "C" {
 const char* ss_last_error(void);
 /* Library/ABI version and the GPU architecture the kernels were compiled for ("gfx950"). */
 /* Bumped whenever a struct layout or an entry-point signature changes (3: ss_gemm_epilogue column-statistics fields, the plan /
- * attention-image / LayerNorm-workspace entry points, ss_dtw_cumulative; 4: ss_loss_index_tables; 5: gate recomputation arguments of ss_bn_backward_sums / ss_bn_backward_apply; 7: ss_split_planes / ss_gemm_planes, ss_dw_job.flags, up to 24 jobs per grouped launch; 8: ss_stft_logmel_fft, the rejected-frame counter behind the matrix of ss_phoneme_confusion; 9: planes_hi / planes_lo / planes_only of ss_gemm_epilogue, dropout groups of the GEMM epilogue are row-major; 10: ss_emg_features_batch; 11: the ss_voc_* vocoder entry points; 12: the ragged-batch inference entry points ss_bn_apply_ragged, ss_relpos_attention_forward_ragged, ss_plan_forward_ragged; 13: ss_ctc_beam_search / ss_ctc_beam_workspace_bytes; 14: ss_word_lm, ss_ctc_word_beam_search / ss_ctc_word_beam_workspace_bytes, ss_word_ngram_score; 15: ss_audio_resample_batch / ss_audio_resample_supported / ss_audio_resample_limits, ss_audio_level_batch; 16: ss_spectral_gate_profile / ss_spectral_gate_batch / ss_spectral_gate_limits; 17: ss_stft_logmel_fft_backward / ss_stft_logmel_fft_backward_workspace_bytes; 18: ss_ctc_align / ss_ctc_align_workspace_bytes; 19: ss_spectral_gate_ns_batch; 20: ss_iir_filtfilt / ss_iir_filtfilt_workspace_bytes / ss_linear_resample / ss_reflect_pad removed, a single signal is a batch of one; 21: ss_word_state_lm, ss_ctc_word_state_beam_search / ss_ctc_word_state_beam_workspace_bytes, ss_word_state_score; 22: ss_edit_distance / ss_edit_distance_workspace_bytes, ss_nbest_risk).  Bindings must compare it with SS_ABI_VERSION at load time: a stale
+ * attention-image / LayerNorm-workspace entry points, ss_dtw_cumulative; 4: ss_loss_index_tables; 5: gate recomputation arguments of ss_bn_backward_sums / ss_bn_backward_apply; 7: ss_split_planes / ss_gemm_planes, ss_dw_job.flags, up to 24 jobs per grouped launch; 8: ss_stft_logmel_fft, the rejected-frame counter behind the matrix of ss_phoneme_confusion; 9: planes_hi / planes_lo / planes_only of ss_gemm_epilogue, dropout groups of the GEMM epilogue are row-major; 10: ss_emg_features_batch; 11: the ss_voc_* vocoder entry points; 12: the ragged-batch inference entry points ss_bn_apply_ragged, ss_relpos_attention_forward_ragged, ss_plan_forward_ragged; 13: ss_ctc_beam_search / ss_ctc_beam_workspace_bytes; 14: ss_word_lm, ss_ctc_word_beam_search / ss_ctc_word_beam_workspace_bytes, ss_word_ngram_score; 15: ss_audio_resample_batch / ss_audio_resample_supported / ss_audio_resample_limits, ss_audio_level_batch; 16: ss_spectral_gate_profile / ss_spectral_gate_batch / ss_spectral_gate_limits; 17: ss_stft_logmel_fft_backward / ss_stft_logmel_fft_backward_workspace_bytes; 18: ss_ctc_align / ss_ctc_align_workspace_bytes; 19: ss_spectral_gate_ns_batch; 20: ss_iir_filtfilt / ss_iir_filtfilt_workspace_bytes / ss_linear_resample / ss_reflect_pad removed, a single signal is a batch of one; 21: ss_word_state_lm, ss_ctc_word_state_beam_search / ss_ctc_word_state_beam_workspace_bytes, ss_word_state_score; 22: ss_edit_distance / ss_edit_distance_workspace_bytes, ss_nbest_risk; 23: ss_ctc_nbest_logp / ss_ctc_nbest_workspace_bytes / ss_ctc_nbest_backward, ss_nbest_expected_risk).  Bindings must compare it with SS_ABI_VERSION at load time: a stale
  * library paired with newer headers would otherwise read garbage struct fields instead of failing. */
-#define SS_ABI_VERSION 22
+#define SS_ABI_VERSION 23
 int ss_abi_version(void);
 const char* ss_target_arch(void);
 
@@ -539,6 +539,47 @@ int ss_edit_distance(const int32_t* tokens, int64_t n_tokens, const int64_t* seq
  *   sequences of the group that exist.  Entries of risk outside every group are not written.  n_groups = 0 launches nothing. */
 int ss_nbest_risk(const int32_t* tokens, int64_t n_tokens, const int64_t* seqs, int64_t n_seq, const int64_t* groups, int n_groups, int max_k,
                   const float* weights, int32_t* dmat, int64_t n_dmat, double* risk, int32_t* pick, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * n-best lists as a training criterion (csrc/ctc.hip): the full-sum CTC log-likelihood of SEVERAL label strings per utterance with its
+ * gradient, and the expected risk of the lists under their own posterior (minimum expected word error, MWER).
+ * Notation: utterance u has the frames [f0_u, f0_u + T_u) of the packed (rows, ld) f32 logits, p_t(c) = softmax(logit_t)[c] over the V classes
+ *   (lse as for ss_ctc_loss), and a list of K_u >= 0 hypotheses; a hypothesis is a string of S <= 511 class numbers, never the blank.
+ * Tables: utt (device, int64 x4 per utterance) = first frame, frames, first hypothesis, K (utterances do not share frames; the hypotheses of a
+ *   list are consecutive); hyp (device, int64 x3 per hypothesis) = first label in targets, S, offset (floats) of the hypothesis' T_u (2 S + 1)
+ *   block in the alpha and the beta workspace (blocks do not overlap).
+ * ss_ctc_nbest_logp: logp[h] = ln sum_{alignments of h} prod_t p_t(.), f32 natural log: exactly -nll of ss_ctc_loss's alpha / beta kernel, which
+ *   runs unchanged (for a list of one hypothesis that is the reference the bits equal -nll); -inf where no alignment exists (T < S + repeats,
+ *   T = 0 < S).  max_target_len >= the longest hypothesis (it sizes the launch: 2 max_target_len + 1 <= 1024 states, LDS as for ss_ctc_loss).
+ *   workspace: ss_ctc_nbest_workspace_bytes(n_hyp, ws_floats) bytes, ws_floats = the sum of the blocks; needs no initialisation and is what
+ *   ss_ctc_nbest_backward reads (descriptors, alpha, beta); -1 = bad arguments.
+ *   Bad table entries are cut short on the device, never followed: a hypothesis that belongs to no list, whose utterance leaves [0, rows), whose
+ *   labels leave targets[0, n_targets) or are no class or the blank, that is longer than max_target_len or whose block leaves the workspace
+ *   gets logp = -inf and touches nothing; every other hypothesis is unaffected.  n_hyp = 0 launches nothing.
+ * ss_ctc_nbest_backward: for a cotangent g[h] per hypothesis the complete rows x ld gradient
+ *     dlogits[t][c] = sum_{h in list(u), logp_h finite} g_h (occ_h[t][c] - p_t(c)),
+ *   occ_h[t][c] = sum_{s: ext_label_h(s) = c} alpha_t(s) beta_t(s) / (p_t(c) P_h), the posterior that h emits class c at frame t.  A hypothesis
+ *   with logp = -inf contributes nothing whatever its g (no NaN, unlike ss_ctc_loss).  EVERY frame is written: frames outside every utterance,
+ *   frames of an utterance with K_u = 0 and the columns c >= V get 0 (the logits of such frames are not read).  The hypotheses of a frame are
+ *   accumulated in ascending list order by one wave; no float atomics on global memory.  The same tables, targets, workspace and logp as the
+ *   forward call; whatever the tables hold, nothing outside the workspace, targets and the rows is touched.
+ * ss_nbest_expected_risk: groups (device, int64 x2 per list) = first hypothesis, 0 <= K <= 128.  With all sums over the entries of FINITE logp,
+ *   in f64 and ascending order:  post_k = softmax_k(scale logp_k),  e_u = mean_k cost_k,  risk_u = sum_k post_k (cost_k - e_u),
+ *   loss[0] = mean of risk_u over the n_used lists that have a finite entry (0 if there is none), and
+ *     dlogp[k] = d loss / d logp_k = scale post_k (cost_k - e_u - risk_u) / n_used.
+ *   Outputs: loss (f32), risk (n_groups, f64), post and dlogp (n_hyp, f32 roundings of the f64 values); entries of non-finite logp, of no list
+ *   or of a refused list get post = dlogp = 0.  A list without a finite entry (K = 0 included) has no posterior: risk NaN, not part of the mean.
+ *   Bad table entries: a K outside 0 .. 128 or a list that leaves [0, n_hyp) gives risk NaN and zero cotangents for that list; the other lists
+ *   are unaffected.  Costs are finite.  One launch (one workgroup, a wave per list at a time). */
+int64_t ss_ctc_nbest_workspace_bytes(int64_t n_hyp, int64_t ws_floats);
+int ss_ctc_nbest_logp(const float* logits, int64_t ld, int V, int blank, int64_t rows, const float* lse, const int64_t* utt_dev, int n_utt,
+                      const int64_t* hyp_dev, int64_t n_hyp, int max_target_len, const int32_t* targets, int64_t n_targets, void* workspace,
+                      int64_t ws_floats, float* logp, void* stream);
+int ss_ctc_nbest_backward(const float* logits, int64_t ld, int V, int blank, int64_t rows, const float* lse, const int64_t* utt_dev, int n_utt,
+                          int64_t n_hyp, const int32_t* targets, const void* workspace, int64_t ws_floats, const float* logp, const float* g,
+                          float* dlogits, void* stream);
+int ss_nbest_expected_risk(const float* logp, const float* cost, int64_t n_hyp, const int64_t* groups, int n_groups, double scale, float* loss,
+                           double* risk, float* post, float* dlogp, void* stream);
 
 /* AdamW over a flat f32 arena (transduction_model.py:178,210).  step is 1-based. */
 int ss_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,

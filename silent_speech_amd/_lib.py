@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.environ.get('SS_AMD_LIBRARY') or os.path.join(_HERE, 'lib', 'libsilent_speech_hip.so')      # override: A/B runs of two builds on one box
 
 SS_F32, SS_BF16, SS_F64, SS_F32X3 = 0, 1, 2, 3
-ABI_VERSION = 22         # include/silent_speech_hip.h: SS_ABI_VERSION (struct layouts / signatures this binding was written against)
+ABI_VERSION = 23         # include/silent_speech_hip.h: SS_ABI_VERSION (struct layouts / signatures this binding was written against)
 OP_KC, OP_OC = 0, 1
 
 
@@ -122,6 +122,9 @@ SIGNATURES = {
     'ss_ctc_align': [_P, _L, _I, _I, _L, _P, _P, _I, _L, _I, _P, _L, _P, _P, _P, _P, _P, _P, _P],
     'ss_edit_distance': [_P, _L, _P, _L, _P, _L, _P, _P, _P, _P, _L, _P, _P],
     'ss_nbest_risk': [_P, _L, _P, _L, _P, _I, _I, _P, _P, _L, _P, _P, _P],
+    'ss_ctc_nbest_logp': [_P, _L, _I, _I, _L, _P, _P, _I, _P, _L, _I, _P, _L, _P, _L, _P, _P],
+    'ss_ctc_nbest_backward': [_P, _L, _I, _I, _L, _P, _P, _I, _L, _P, _P, _L, _P, _P, _P, _P],
+    'ss_nbest_expected_risk': [_P, _P, _L, _P, _I, ctypes.c_double, _P, _P, _P, _P, _P],
     'ss_adamw_step': [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _F, _P],
     'ss_cast_f32': [_P, _P, _I, _L, _P],
     'ss_soft_clip': [_P, _P, _L, _I, _P, _P, _F, _F, _P],
@@ -182,6 +185,7 @@ _HOST_FUNCS = {'ss_stft_logmel_fft_backward_workspace_bytes': ([_I, _I], ctypes.
                'ss_ctc_word_state_beam_workspace_bytes': ([_I, _L, _I], ctypes.c_int64),
                'ss_ctc_align_workspace_bytes': ([_I, _L, _I], ctypes.c_int64),
                'ss_edit_distance_workspace_bytes': ([_L, _L], ctypes.c_int64),
+               'ss_ctc_nbest_workspace_bytes': ([_L, _L], ctypes.c_int64),
                'ss_voc_blob_bytes': ([_I, _I, _I], ctypes.c_int64),
                'ss_voc_workspace_bytes': ([_L, _I, ctypes.POINTER(ctypes.c_int), _I], ctypes.c_int64),
                'ss_voc_supported': ([_I, _I, _I, _I, _I], ctypes.c_int),

@@ -269,23 +269,38 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const float* __restrict__
     }
 }
 
+// The argument checks and the alpha / beta launch ss_ctc_loss and ss_ctc_nbest_logp share: ONE definition of the kernel's geometry and of its LDS grant.
+// n descriptors (n > 0), every one a workgroup pair; the kernel is indifferent to descriptors that share frames (it reads desc[u], writes its own
+// workspace block and nll[u]).
+static int ctc_check_classes(const char* who, int64_t ld, int V, int blank, int64_t n, int max_target_len)
+{
+    SS_CHECK(V >= 1 && V <= 4096 && blank >= 0 && blank < V && ld >= V, "%s: bad class count %d / blank %d / row stride %lld", who, V, blank, (long long)ld);
+    SS_CHECK(n >= 0 && max_target_len >= 0, "%s: negative sizes", who);
+    SS_CHECK(2 * max_target_len + 1 <= CTC_MAX_STATES, "%s: target length %d exceeds the %d-label limit", who, max_target_len, (CTC_MAX_STATES - 1) / 2);
+    return 0;
+}
+static int ctc_launch_alpha_beta(const char* who, const float* logits, int64_t ld, int V, int blank, const float* lse, const int64_t* desc, int n, int max_target_len,
+                                 const int32_t* targets, float* alpha_ws, float* beta_ws, float* nll, void* stream)
+{
+    const int sp_cap = 2 * max_target_len + 1;
+    const int W = (sp_cap + CTC_C - 1) / CTC_C;                          // compute waves per (utterance, direction): 128 states each; + 1 loader wave
+    const size_t smem = sizeof(float) * ((size_t)CTC_NB * CTC_FC * V + (size_t)W * CTC_R + W + 1 + (size_t)W * (64 + CTC_B));
+    SS_CHECK(smem <= 160 * 1024, "%s: %zu bytes of LDS needed", who, smem);
+    static size_t granted = 0;
+    if (granted < smem) { if (!ss_grant_lds((const void*)ctc_alpha_beta_kernel, smem)) { ss_set_error("%s: cannot reserve %zu bytes of LDS", who, smem); return 1; } granted = smem; }
+    SS_LAUNCH(ctc_alpha_beta_kernel, dim3(2 * n), dim3((W + 1) * 64), smem, stream, logits, (long long)ld, V, blank, lse, (const long long*)desc, targets, alpha_ws, beta_ws, nll, W);
+    return 0;
+}
+
 extern "C" int ss_ctc_loss(const float* logits, int64_t ld, int V, int blank, const float* lse, const int64_t* desc, int n_utt, int max_target_len,
                            int64_t rows, const int32_t* targets, float* alpha_ws, float* beta_ws, float* nll, float* dlogits, float* loss, void* stream)
 {
     SS_CHECK(logits && lse && dlogits && loss, "ss_ctc_loss: null pointer");
-    SS_CHECK(V >= 1 && V <= 4096 && blank >= 0 && blank < V && ld >= V, "ss_ctc_loss: bad class count %d / blank %d / row stride %lld", V, blank, (long long)ld);
-    SS_CHECK(n_utt >= 0 && max_target_len >= 0, "ss_ctc_loss: negative sizes");
-    const int sp_cap = 2 * max_target_len + 1;
-    SS_CHECK(sp_cap <= CTC_MAX_STATES, "ss_ctc_loss: target length %d exceeds the %d-label limit", max_target_len, (CTC_MAX_STATES - 1) / 2);
+    if (ctc_check_classes("ss_ctc_loss", ld, V, blank, n_utt, max_target_len)) return 1;
     if (n_utt > 0) {
         SS_CHECK(desc && alpha_ws && beta_ws && nll, "ss_ctc_loss: null workspace");
         SS_CHECK(targets || max_target_len == 0, "ss_ctc_loss: null targets");
-        const int W = (sp_cap + CTC_C - 1) / CTC_C;                      // compute waves per (utterance, direction): 128 states each; + 1 loader wave
-        const size_t smem = sizeof(float) * ((size_t)CTC_NB * CTC_FC * V + (size_t)W * CTC_R + W + 1 + (size_t)W * (64 + CTC_B));
-        SS_CHECK(smem <= 160 * 1024, "ss_ctc_loss: %zu bytes of LDS needed", smem);
-        static size_t granted = 0;
-        if (granted < smem) { if (!ss_grant_lds((const void*)ctc_alpha_beta_kernel, smem)) { ss_set_error("ss_ctc_loss: cannot reserve %zu bytes of LDS", smem); return 1; } granted = smem; }
-        SS_LAUNCH(ctc_alpha_beta_kernel, dim3(2 * n_utt), dim3((W + 1) * 64), smem, stream, logits, (long long)ld, V, blank, lse, (const long long*)desc, targets, alpha_ws, beta_ws, nll, W);
+        if (ctc_launch_alpha_beta("ss_ctc_loss", logits, ld, V, blank, lse, desc, n_utt, max_target_len, targets, alpha_ws, beta_ws, nll, stream)) return 1;
         SS_LAUNCH_CHECK("ss_ctc_loss(alpha/beta)");
     }
     {
@@ -294,5 +309,238 @@ extern "C" int ss_ctc_loss(const float* logits, int64_t ld, int V, int blank, co
                   (long long)rows, targets, alpha_ws, beta_ws, nll, n_utt > 0 ? 1.f / (float)n_utt : 0.f, dlogits, loss);
         SS_LAUNCH_CHECK("ss_ctc_loss(grad)");
     }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------------
+// n-best lists: the full-sum log-likelihood of SEVERAL label strings per utterance, with a gradient (ss_ctc_nbest_logp / ss_ctc_nbest_backward), and the
+// expected risk of the lists under their own posterior (ss_nbest_expected_risk); the header states the definitions.
+//   forward  : the two tables become ordinary 5-column descriptors on the device (ctc_nbest_desc_kernel, one thread per hypothesis; whatever the tables
+//              hold, a descriptor that leaves the logits, targets or the workspace, or names a label that is no class, becomes "no frames, one label":
+//              the alpha / beta kernel then writes nll = +inf and touches nothing else), ctc_alpha_beta_kernel runs on them unchanged, and one small
+//              launch turns nll into logp = -nll (a sign flip: the bits of -plan.nll).
+//   backward : ctc_grad_kernel finds "the" utterance of a frame; here a frame belongs to K hypotheses.  One wave per packed frame walks the list of its
+//              utterance in ascending order, per hypothesis the occupancy bins of ctc_grad_kernel in the wave's LDS slice, folded with the cotangent
+//              g_h into a second slice (class c is only ever touched by lane c % 64: no atomics on it, none on global memory); G = sum g_h is carried
+//              and G p_t(c) subtracted once at the end.  No wave talks to another: no polling, no workgroup barrier.
+namespace {
+constexpr int NB_UD = 4, NB_HD = 3;                                     // utterance table: first frame, frames, first hypothesis, K; hypothesis table: first label, S, workspace offset
+constexpr long long NB_MAX_HYP = 1ll << 24;
+__host__ __device__ inline size_t nbest_alpha_offset(long long n_hyp) { return (((size_t)(n_hyp > 1 ? n_hyp : 1) * CD * sizeof(long long)) + 63) & ~(size_t)63; }
+}
+
+__global__ __launch_bounds__(256) void ctc_nbest_desc_kernel(const long long* __restrict__ utt, int n_utt, const long long* __restrict__ hyp, long long n_hyp,
+                                                             long long rows, int V, int blank, int max_s, const int* __restrict__ targets, long long n_targets,
+                                                             long long ws_floats, long long* __restrict__ desc)
+{
+    const long long h = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (h >= n_hyp) return;
+    long long f0 = 0, T = 0;
+    bool ok = false;
+    for (int u = 0; u < n_utt && !ok; ++u) {                             // the first utterance whose list holds h
+        const long long h0 = utt[u * NB_UD + 2], K = utt[u * NB_UD + 3];
+        if (h0 < 0 || K <= 0 || h < h0 || h - h0 >= K) continue;
+        f0 = utt[u * NB_UD]; T = utt[u * NB_UD + 1];
+        ok = true;
+    }
+    const long long g0 = hyp[h * NB_HD], S = hyp[h * NB_HD + 1], w0 = hyp[h * NB_HD + 2];
+    ok = ok && f0 >= 0 && T >= 0 && f0 <= rows && T <= rows - f0 && T < (1ll << 30);
+    ok = ok && S >= 0 && S <= max_s && g0 >= 0 && g0 <= n_targets && S <= n_targets - g0;
+    ok = ok && w0 >= 0 && w0 <= ws_floats && T * (2 * S + 1) <= ws_floats - w0;
+    if (ok) for (long long j = 0; j < S; ++j) { const int c = targets[g0 + j]; if (c < 0 || c >= V || c == blank) ok = false; }
+    long long* d = desc + h * CD;
+    if (ok) { d[0] = f0; d[1] = T; d[2] = g0; d[3] = S; d[4] = w0; }
+    else { d[0] = -1; d[1] = 0; d[2] = 0; d[3] = 1; d[4] = 0; }          // refused: no frames, one label -> nll = +inf, nothing read or written
+}
+
+__global__ __launch_bounds__(256) void ctc_nbest_negate_kernel(float* __restrict__ x, long long n)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) x[i] = -x[i];
+}
+
+__global__ __launch_bounds__(256) void ctc_nbest_grad_kernel(const float* __restrict__ logits, long long ld, int V, int blank, const float* __restrict__ lse,
+                                                             const long long* __restrict__ utt, int n_utt, long long n_hyp, long long rows,
+                                                             const long long* __restrict__ desc, const int* __restrict__ targets,
+                                                             const float* __restrict__ alpha, const float* __restrict__ beta, const float* __restrict__ logp,
+                                                             const float* __restrict__ gout, float* __restrict__ dlogits)
+{
+    SS_DYN_SMEM(smem);
+    const int lane = threadIdx.x & 63, w = wave_uniform(threadIdx.x >> 6), wpb = blockDim.x >> 6;
+    float* bins = (float*)smem + (size_t)w * 2 * V;                      // occupancy of the current hypothesis
+    float* acc = bins + V;                                               // sum_h g_h occ_h[t][c]; entry c belongs to lane c % 64
+    for (long long r = (long long)blockIdx.x * wpb + w; r < rows; r += (long long)gridDim.x * wpb) {
+        // the frame's utterance: the first entry that covers it; entries that leave [0, rows) cover nothing (as ctc_utt_frames clamps them)
+        long long f0 = 0, T = 0, h0 = 0, K = 0;
+        for (int u = 0; u < n_utt; ++u) {
+            const long long a = utt[u * NB_UD], n = utt[u * NB_UD + 1];
+            if (a < 0 || n <= 0 || a > rows || n > rows - a || r < a || r - a >= n) continue;
+            f0 = a; T = n; h0 = utt[u * NB_UD + 2]; K = utt[u * NB_UD + 3];
+            break;
+        }
+        if (h0 < 0 || K < 0 || h0 > n_hyp || K > n_hyp - h0) K = 0;
+        float* d = dlogits + r * ld;
+        for (int c = lane; c < V; c += 64) acc[c] = 0.f;
+        float G = 0.f;
+        bool any = false;
+        for (long long k = 0; k < K; ++k) {
+            const long long h = h0 + k;
+            const long long* dh = desc + h * CD;
+            if (dh[0] != f0 || dh[1] != T) continue;                     // refused by the forward pass, or claimed by an earlier utterance
+            const float lph = logp[h], gh = gout[h];
+            if (!(fabsf(lph) < INFINITY) || gh == 0.f) continue;         // no alignment (or no cotangent): contributes nothing
+            const long long g0 = dh[2], S = dh[3], w0 = dh[4];
+            const int SP = (int)(2 * S + 1);
+            const float* a = alpha + w0 + (r - f0) * SP; const float* b = beta + w0 + (r - f0) * SP;
+            // alpha / beta are log2 values with the finite sentinel CTC_NEG for "no path" (a sum with a sentinel in it stays below CTC_NEG / 2)
+            float m = CTC_NEG;
+            for (int s = lane; s < SP; s += 64) m = fmaxf(m, a[s] + b[s]);
+            m = wave_max(m);
+            for (int c = lane; c < V; c += 64) bins[c] = 0.f;
+            wave_lds_sync();
+            for (int s = lane; s < SP; s += 64) {
+                const float v = a[s] + b[s];
+                if (v > 0.5f * CTC_NEG) atomicAdd(&bins[(s & 1) ? targets[g0 + (s >> 1)] : blank], fast_exp2(v - m));
+            }
+            wave_lds_sync();
+            const float L = lse[r], base = m * LN2_F - lph;
+            for (int c = lane; c < V; c += 64) {
+                const float occ = bins[c];
+                if (occ > 0.f) acc[c] += gh * expf(logf(occ) + base - (logits[r * ld + c] - L));
+            }
+            G += gh;
+            any = true;
+            wave_lds_sync();
+        }
+        if (any) {
+            const float L = lse[r];
+            for (int c = lane; c < ld; c += 64) d[c] = c < V ? acc[c] - G * expf(logits[r * ld + c] - L) : 0.f;
+        } else {
+            for (int c = lane; c < ld; c += 64) d[c] = 0.f;              // outside every utterance, K = 0, nothing feasible: exactly 0, the logits are not read
+        }
+        wave_lds_sync();
+    }
+}
+
+// Expected risk of n-best lists.  ONE workgroup of four waves, a wave per list at a time; every sum in f64 and in ascending k (each lane runs the same
+// K <= 128 additions over the wave's LDS copy of the list: broadcast reads, no divergence, no reduction tree whose order would have to be stated).
+// Three phases with a workgroup barrier between them: count the lists that have a finite entry (n_used enters every cotangent), the lists themselves,
+// the mean of their risks in ascending list order.
+__global__ __launch_bounds__(256) void nbest_expected_risk_kernel(const float* __restrict__ logp, const float* __restrict__ cost, long long n_hyp,
+                                                                  const long long* __restrict__ groups, int n_groups, double scale,
+                                                                  float* __restrict__ loss, double* __restrict__ risk, float* __restrict__ post, float* __restrict__ dlogp)
+{
+    __shared__ double sz[4][128], sc[4][128];
+    __shared__ int s_used;
+    const int tid = threadIdx.x, lane = tid & 63, w = wave_uniform(tid >> 6);
+    if (tid == 0) s_used = 0;
+    __syncthreads();
+    for (int g = tid; g < n_groups; g += 256) {
+        const long long first = groups[2 * g], K = groups[2 * g + 1];
+        if (first < 0 || K < 0 || K > 128 || first > n_hyp || K > n_hyp - first) continue;
+        bool fin = false;
+        for (int k = 0; k < (int)K; ++k) fin = fin || fabsf(logp[first + k]) < INFINITY;
+        if (fin) atomicAdd(&s_used, 1);
+    }
+    __syncthreads();
+    const int n_used = s_used;
+    for (int g = w; g < n_groups; g += 4) {
+        const long long first = groups[2 * g], Kl = groups[2 * g + 1];
+        if (first < 0 || Kl < 0 || Kl > 128 || first > n_hyp || Kl > n_hyp - first) { if (lane == 0) risk[g] = __builtin_nan(""); continue; }
+        const int K = (int)Kl;
+        for (int k = lane; k < K; k += 64) {
+            const float lp = logp[first + k];
+            sz[w][k] = fabsf(lp) < INFINITY ? scale * (double)lp : -__builtin_inf();
+            sc[w][k] = (double)cost[first + k];
+        }
+        wave_lds_sync();
+        double mx = -__builtin_inf(), ce = 0.0;
+        int nf = 0;
+        for (int k = 0; k < K; ++k) { const double z = sz[w][k]; if (z > -__builtin_inf()) { ++nf; mx = z > mx ? z : mx; ce += sc[w][k]; } }
+        if (nf == 0) { if (lane == 0) risk[g] = __builtin_nan(""); wave_lds_sync(); continue; }     // no posterior exists: not one of the lists of the mean
+        ce /= (double)nf;
+        double Z = 0.0, rk = 0.0;
+        for (int k = 0; k < K; ++k) { const double z = sz[w][k]; if (z > -__builtin_inf()) Z += exp(z - mx); }
+        for (int k = 0; k < K; ++k) { const double z = sz[w][k]; if (z > -__builtin_inf()) rk += exp(z - mx) / Z * (sc[w][k] - ce); }
+        if (lane == 0) risk[g] = rk;
+        for (int k = lane; k < K; k += 64) {
+            const double z = sz[w][k];
+            if (z > -__builtin_inf()) {
+                const double p = exp(z - mx) / Z;
+                post[first + k] = (float)p;
+                dlogp[first + k] = (float)(scale * p * (sc[w][k] - ce - rk) / (double)n_used);
+            }
+        }
+        wave_lds_sync();
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double tot = 0.0;
+        for (int g = 0; g < n_groups; ++g) { const double v = risk[g]; if (v == v) tot += v; }
+        loss[0] = n_used > 0 ? (float)(tot / (double)n_used) : 0.f;
+    }
+}
+
+extern "C" int64_t ss_ctc_nbest_workspace_bytes(int64_t n_hyp, int64_t ws_floats)
+{
+    if (n_hyp < 0 || n_hyp > NB_MAX_HYP || ws_floats < 0 || ws_floats > (1ll << 40)) return -1;
+    return (int64_t)nbest_alpha_offset(n_hyp) + 2 * (int64_t)sizeof(float) * (ws_floats > 1 ? ws_floats : 1);
+}
+
+extern "C" int ss_ctc_nbest_logp(const float* logits, int64_t ld, int V, int blank, int64_t rows, const float* lse, const int64_t* utt, int n_utt,
+                                 const int64_t* hyp, int64_t n_hyp, int max_target_len, const int32_t* targets, int64_t n_targets, void* workspace,
+                                 int64_t ws_floats, float* logp, void* stream)
+{
+    SS_CHECK(logits && lse, "ss_ctc_nbest_logp: null pointer");
+    if (ctc_check_classes("ss_ctc_nbest_logp", ld, V, blank, n_hyp, max_target_len)) return 1;
+    SS_CHECK(n_utt >= 0 && rows >= 0 && n_targets >= 0 && ws_floats >= 0 && n_hyp <= NB_MAX_HYP, "ss_ctc_nbest_logp: bad sizes");
+    if (n_hyp == 0) return 0;
+    SS_CHECK(hyp && workspace && logp && (utt || n_utt == 0), "ss_ctc_nbest_logp: null table or workspace");
+    SS_CHECK(targets || n_targets == 0, "ss_ctc_nbest_logp: null targets");
+    long long* desc = (long long*)workspace;
+    float* alpha_ws = (float*)((char*)workspace + nbest_alpha_offset(n_hyp));
+    float* beta_ws = alpha_ws + (ws_floats > 1 ? ws_floats : 1);
+    SS_LAUNCH(ctc_nbest_desc_kernel, dim3((unsigned)((n_hyp + 255) / 256)), dim3(256), 0, stream, (const long long*)utt, n_utt, (const long long*)hyp, (long long)n_hyp,
+              (long long)rows, V, blank, max_target_len, targets, (long long)n_targets, (long long)ws_floats, desc);
+    SS_LAUNCH_CHECK("ss_ctc_nbest_logp(descriptors)");
+    if (ctc_launch_alpha_beta("ss_ctc_nbest_logp", logits, ld, V, blank, lse, (const int64_t*)desc, (int)n_hyp, max_target_len, targets, alpha_ws, beta_ws, logp, stream)) return 1;
+    SS_LAUNCH_CHECK("ss_ctc_nbest_logp(alpha/beta)");
+    SS_LAUNCH(ctc_nbest_negate_kernel, dim3((unsigned)((n_hyp + 255) / 256)), dim3(256), 0, stream, logp, (long long)n_hyp);
+    SS_LAUNCH_CHECK("ss_ctc_nbest_logp(sign)");
+    return 0;
+}
+
+extern "C" int ss_ctc_nbest_backward(const float* logits, int64_t ld, int V, int blank, int64_t rows, const float* lse, const int64_t* utt, int n_utt,
+                                     int64_t n_hyp, const int32_t* targets, const void* workspace, int64_t ws_floats, const float* logp, const float* g,
+                                     float* dlogits, void* stream)
+{
+    SS_CHECK(V >= 1 && V <= 4096 && blank >= 0 && blank < V && ld >= V, "ss_ctc_nbest_backward: bad class count %d / blank %d / row stride %lld", V, blank, (long long)ld);
+    SS_CHECK(n_utt >= 0 && rows >= 0 && ws_floats >= 0 && n_hyp >= 0 && n_hyp <= NB_MAX_HYP, "ss_ctc_nbest_backward: bad sizes");
+    if (rows == 0) return 0;
+    SS_CHECK(logits && lse && dlogits, "ss_ctc_nbest_backward: null pointer");
+    if (n_hyp == 0) n_utt = 0;                                           // nothing was scored: every frame gets 0
+    SS_CHECK(n_utt == 0 || (utt && workspace && logp && g), "ss_ctc_nbest_backward: null table or workspace");
+    const long long* desc = (const long long*)workspace;
+    const float* alpha_ws = n_utt ? (const float*)((const char*)workspace + nbest_alpha_offset(n_hyp)) : nullptr;
+    const float* beta_ws = n_utt ? alpha_ws + (ws_floats > 1 ? ws_floats : 1) : nullptr;
+    int wpb = 8192 / V; if (wpb > 4) wpb = 4; if (wpb < 1) wpb = 1;    // two V-float slices per wave inside the 64 KiB every kernel may use
+    long long blocks = (rows + wpb - 1) / wpb; if (blocks > 8192) blocks = 8192;
+    SS_LAUNCH(ctc_nbest_grad_kernel, dim3((unsigned)blocks), dim3(64 * wpb), sizeof(float) * 2 * V * wpb, stream, logits, (long long)ld, V, blank, lse, (const long long*)utt, n_utt,
+              (long long)n_hyp, (long long)rows, desc, targets, alpha_ws, beta_ws, logp, g, dlogits);
+    SS_LAUNCH_CHECK("ss_ctc_nbest_backward");
+    return 0;
+}
+
+extern "C" int ss_nbest_expected_risk(const float* logp, const float* cost, int64_t n_hyp, const int64_t* groups, int n_groups, double scale, float* loss,
+                                      double* risk, float* post, float* dlogp, void* stream)
+{
+    SS_CHECK(n_hyp >= 0 && n_hyp <= NB_MAX_HYP && n_groups >= 0 && n_groups <= 65535, "ss_nbest_expected_risk: %lld hypotheses in %d lists", (long long)n_hyp, n_groups);
+    SS_CHECK(loss && (n_groups == 0 || (groups && risk)) && (n_hyp == 0 || (logp && cost && post && dlogp)), "ss_nbest_expected_risk: null pointer");
+    if (n_hyp > 0) {                                                     // entries of no list, without a posterior or of a refused list: 0
+        SS_CHECK(ss_memset_async(post, 0, sizeof(float) * (size_t)n_hyp, stream) && ss_memset_async(dlogp, 0, sizeof(float) * (size_t)n_hyp, stream),
+                 "ss_nbest_expected_risk: memset failed");
+    }
+    SS_LAUNCH(nbest_expected_risk_kernel, dim3(1), dim3(256), 0, stream, logp, cost, (long long)n_hyp, (const long long*)groups, n_groups, scale, loss, risk, post, dlogp);
+    SS_LAUNCH_CHECK("ss_nbest_expected_risk");
     return 0;
 }

@@ -16,6 +16,10 @@
                                              pairs in one launch (csrc/edit_distance.hip); word_errors / cer: the jiwer measures of transcripts
     mbr_rerank(nbest, space=..)              minimum-Bayes-risk choice from n-best lists (all K^2 word distances per list on the device);
                                              oracle_errors: the best hypothesis of every list against its reference
+    nbest_logp(pred, lengths, hyps)          full-sum CTC log-likelihood of arbitrary label strings, several per utterance, with a gradient
+                                             (csrc/ctc.hip); nbest_logp_utterances; rescore_nbest: exact scores for the lists of beam_decode
+    mwer_loss(pred, example, space=..)       minimum expected word error over the model's own n-best lists (+ ctc_weight * ctc_loss);
+                                             train_model(.., mwer=dict(..)) trains on it
     test(model, testset, device)             :30-58 -> WER; decoder='greedy' (default) or 'beam'; mbr=K, details=True
     train_model(trainset, devset, device)    :61-117 (AdamW, warm-up, x2 gradient accumulation, MultiStepLR)
 
@@ -1146,6 +1150,163 @@ def align(model, testset, device, *, batch_size=8):
     return out
 
 
+MAX_NBEST_LABELS = 511
+
+
+class _NbestPlan(object):
+    """The tables of ss_ctc_nbest_logp (include/silent_speech_hip.h) for one list of label strings per utterance, as host arrays: utt (n, 4) =
+    first frame, frames, first hypothesis, K; hyp (H, 3) = first label, S, workspace offset; the flat labels (one spare entry: never an empty
+    upload).  Hypotheses are numbered utterance by utterance, in list order."""
+
+    def __init__(self, who, first, frames, hyps, V, blank):
+        if len(hyps) != len(frames):
+            raise ValueError('%s: %d lists for %d utterances' % (who, len(hyps), len(frames)))
+        if not (0 <= blank < V):
+            raise ValueError('%s: blank %d is not one of the %d classes' % (who, blank, V))
+        utt, hyp, flat, ws, at = [], [], [], 0, 0
+        for u, (f0, T, lst) in enumerate(zip(first, frames, hyps)):
+            lst = [np.asarray(y.detach().cpu() if isinstance(y, torch.Tensor) else y, dtype=np.int64).reshape(-1) for y in lst]
+            utt.append((int(f0), int(T), len(hyp), len(lst)))
+            for y in lst:
+                if y.size > MAX_NBEST_LABELS:
+                    raise ValueError('%s: a hypothesis of utterance %d has %d labels (at most %d)' % (who, u, y.size, MAX_NBEST_LABELS))
+                if y.size and (y.min() < 0 or y.max() >= V or (y == blank).any()):
+                    raise ValueError('%s: a hypothesis of utterance %d has a label outside [0, %d) or equal to the blank %d' % (who, u, V, blank))
+                hyp.append((at, y.size, ws))
+                flat.append(y)
+                at += y.size
+                ws += int(T) * (2 * y.size + 1)
+        self.n, self.n_hyp, self.ws_floats = len(utt), len(hyp), ws
+        self.max_s = max([h[1] for h in hyp] or [0])
+        self.sizes = [k for _, _, _, k in utt]
+        self.utt = np.asarray(utt, dtype=np.int64).reshape(len(utt), 4)
+        self.hyp = np.asarray(hyp, dtype=np.int64).reshape(len(hyp), 3)
+        self.flat = np.concatenate(flat + [np.zeros(1, dtype=np.int64)]).astype(np.int32)
+
+    def arrays(self):
+        """What goes up (never an empty array: one spare row each)"""
+        return [self.utt if self.n else np.zeros((1, 4), np.int64), self.hyp if self.n_hyp else np.zeros((1, 3), np.int64), self.flat]
+
+    def bind(self, utt, hyp, targets):
+        self.utt_dev, self.hyp_dev, self.targets = utt[:self.n], hyp[:self.n_hyp], targets
+        return self
+
+
+def _nbest_logp(who, head, V, blank, first, frames, hyps, return_plan):
+    plan = _NbestPlan(who, first, frames, hyps, V, blank)
+    plan.bind(*staging.upload(plan.arrays(), head.device))                # ONE pinned copy, as _CtcPlan
+    logp, _, _ = torch.ops.silent_speech.ctc_nbest_logp(head, plan.utt_dev, plan.hyp_dev, plan.targets, plan.max_s, plan.ws_floats, V, blank)
+    return (logp, plan) if return_plan else logp
+
+
+def _packed_frames(who, pred, lengths):
+    B, T, V = pred.shape
+    frames = [int(n) for n in lengths]
+    if sum(frames) > B * T or any(n < 0 for n in frames):
+        raise ValueError('%s: the lengths do not fit the %d packed frames' % (who, B * T))
+    first = [int(f) for f in np.concatenate([[0], np.cumsum(frames)])[:-1]] if frames else []
+    return first, frames
+
+
+def nbest_logp(pred, lengths, hyps, blank=None, *, return_plan=False):
+    """Full-sum CTC log-likelihood ln P(h | utterance) of ARBITRARY label strings, several per utterance on the same frames (csrc/ctc.hip,
+    ss_ctc_nbest_logp: the alpha / beta kernel of ctc_loss, one workgroup pair per hypothesis).  pred: (rows, T, V) raw model outputs (NOT
+    log-softmaxed), utterances back to back with `lengths` frames each; hyps: one list of int sequences (lists or tensors, at most 511 labels,
+    never the blank) per utterance, possibly empty.  Returns a 1-D f32 tensor of sum K_u values in utterance-then-list order, attached to
+    autograd (-inf where no alignment exists; such entries get no gradient).  blank defaults to V - 1."""
+    B, T, V = pred.shape
+    blank = V - 1 if blank is None else int(blank)
+    first, frames = _packed_frames('nbest_logp', pred, lengths)
+    return _nbest_logp('nbest_logp', pred.reshape(B * T, V).float().contiguous(), V, blank, first, frames, list(hyps), return_plan)
+
+
+def nbest_logp_utterances(logits, hyps, *, return_plan=False):
+    """nbest_logp for the per-utterance logits Model.forward_utterances returns -- (T_b, V) views of ONE (B T_max, >= V) head buffer --: the slots
+    are read in place (first frame b T_max, T_b frames; filler rows and columns are never looked at, and get a zero gradient).  blank = V - 1."""
+    if not logits:
+        return torch.zeros(0, dtype=torch.float32)
+    head, V = logits[0]._base, logits[0].shape[1]
+    B, T = len(logits), max(int(y.shape[0]) for y in logits)
+    if head is None or head.dim() != 2 or head.dtype != torch.float32 or not head.is_contiguous() or head.shape[0] != B * T or \
+            any(y._base is not head or y.shape[1] != V or y.storage_offset() != b * T * head.shape[1] for b, y in enumerate(logits)):
+        raise ValueError('nbest_logp_utterances takes the list Model.forward_utterances returned')
+    return _nbest_logp('nbest_logp_utterances', head, V, V - 1, [b * T for b in range(B)], [int(y.shape[0]) for y in logits], list(hyps), return_plan)
+
+
+def rescore_nbest(pred, lengths, nbest, blank=None):
+    """The n-best lists of beam_decode(.., n_best=K) with every score replaced by the full-sum CTC log-likelihood of its string (the beam's own
+    score is the mass of the paths that survived pruning): the exact weights for mbr_rerank.  No gradient.  Returns lists of (ints, logp)."""
+    nbest = [list(h) for h in nbest]
+    with torch.no_grad():
+        logp = nbest_logp(pred.detach(), lengths, [[ints for ints, _ in h] for h in nbest], blank).cpu().numpy()
+    out, at = [], 0
+    for h in nbest:
+        out.append([(list(ints), float(logp[at + k])) for k, (ints, _) in enumerate(h)])
+        at += len(h)
+    return out
+
+
+def mwer_loss(pred, example, *, space, blank=None, n_best=4, beam_width=16, lm=None, alpha=0.0, beta=0.0, unit='word', scale=1.0, ctc_weight=0.01,
+              add_reference=False, nbest=None, return_details=False):
+    """Minimum expected word error over the model's own n-best lists (ss_nbest_expected_risk in include/silent_speech_hip.h states the risk):
+        sum_k post_k (cost_k - mean cost) per utterance, post = softmax(scale * full-sum log-likelihood) over the list, cost = the word
+        (unit='char': label) errors S + D + I of the hypothesis against example['text_int'], averaged over the utterances with a feasible
+        hypothesis, + ctc_weight * ctc_loss(pred, example).
+    The lists are decoded with beam_decode(n_best=, beam_width=, lm=, alpha=, beta=) from the DETACHED logits (one read-back of labels and lengths)
+    unless nbest= supplies them ([(ints, score), ...] per utterance); they are not differentiated through (a decoded string of more than 511 labels is left out of its list).  add_reference=True appends the reference
+    string to a list that does not hold it.  Words are the runs of labels between `space` labels, interned on the host; then one edit-distance launch
+    over all (reference, hypothesis) pairs, one ctc_nbest_logp, one nbest_expected_risk (and ctc_loss when ctc_weight != 0), costs and
+    likelihoods staying on the device.  Returns the 0-dim loss, attached to autograd; with return_details=True also a dict: 'nbest' (the lists
+    used), 'logp', 'post', 'cost' (flat, utterance-then-list order), 'sizes' (K per utterance) and 'risk' (f64 per utterance, NaN where no
+    hypothesis is feasible)."""
+    B, T, V = pred.shape
+    blank = V - 1 if blank is None else int(blank)
+    space = int(space)
+    first, frames = _packed_frames('mwer_loss', pred, example['lengths'])
+    refs = [[int(c) for c in torch.as_tensor(y).reshape(-1).tolist()] for y in example['text_int']]
+    if len(refs) != len(frames):
+        raise ValueError('mwer_loss: %d transcripts for %d utterances' % (len(refs), len(frames)))
+    if nbest is None:
+        with torch.no_grad():
+            nbest = beam_decode(pred.detach(), frames, blank, beam_width=beam_width, n_best=n_best, lm=lm, alpha=alpha, beta=beta,
+                                space=space if isinstance(lm, (WordNgramLM, WordStateLM)) else None)
+        if n_best == 1:
+            nbest = [[(ints, float('nan'))] for ints in nbest]
+        nbest = [[(ints, score) for ints, score in h if len(ints) <= MAX_NBEST_LABELS] for h in nbest]      # longer than the kernel scores: left out of the list
+    nbest = [[(list(ints), float(score)) for ints, score in h] for h in nbest]
+    if len(nbest) != len(frames):
+        raise ValueError('mwer_loss: %d n-best lists for %d utterances' % (len(nbest), len(frames)))
+    if add_reference:
+        for ref, h in zip(refs, nbest):
+            if all(ints != ref for ints, _ in h):
+                h.append((list(ref), float('nan')))
+    if any(len(h) > MAX_NBEST for h in nbest):
+        raise ValueError('mwer_loss: more than %d hypotheses for one utterance' % MAX_NBEST)
+    logits = pred.reshape(B * T, V).float().contiguous()
+    plan = _NbestPlan('mwer_loss', first, frames, [[ints for ints, _ in h] for h in nbest], V, blank)
+    table, pairs = _TokenTable('mwer_loss'), []
+    for ref, h in zip(refs, nbest):
+        r = table.add(_label_units(ref, space, unit, 'mwer_loss'))
+        pairs.extend((r, table.add(_label_units(ints, space, unit, 'mwer_loss'))) for ints, _ in h)
+    flat, seqs = table.arrays()
+    groups = plan.utt[:, 2:].copy() if plan.n else np.zeros((0, 2), np.int64)
+    up = staging.upload(plan.arrays() + [flat, seqs if len(seqs) else np.zeros((1, 2), np.int64),
+                                         np.asarray(pairs if pairs else [(0, 0)], dtype=np.int32).reshape(-1, 2),
+                                         groups if len(groups) else np.zeros((1, 2), np.int64)], logits.device)            # ONE pinned copy
+    plan.bind(*up[:3])
+    tokens, seqs_d, pairs_d, groups_d = up[3], up[4][:len(seqs)], up[5][:len(pairs)], up[6][:len(groups)]
+    dist, _, _, _ = torch.ops.silent_speech.edit_distance(tokens, seqs_d, pairs_d, False)
+    cost = dist.to(torch.float32)
+    logp, _, _ = torch.ops.silent_speech.ctc_nbest_logp(logits, plan.utt_dev, plan.hyp_dev, plan.targets, plan.max_s, plan.ws_floats, V, blank)
+    risk_loss, risk, post, _ = torch.ops.silent_speech.nbest_expected_risk(logp, cost, groups_d, float(scale))
+    loss = risk_loss[0]
+    if ctc_weight != 0:
+        loss = loss + float(ctc_weight) * ctc_loss(pred, example, blank)
+    if not return_details:
+        return loss
+    return loss, {'nbest': nbest, 'logp': logp.detach(), 'post': post.detach(), 'cost': cost, 'sizes': plan.sizes, 'risk': risk.detach()}
+
+
 def test(model, testset, device, *, batch_size=1, whole_utterances=False, decoder='greedy', beam_width=100, lm=None, alpha=0.0, beta=0.0,
          mbr=None, mbr_scale=1.0, details=False):
     """:30-58.  Default (batch_size=1) = the reference: eval-mode forward of ONE WHOLE utterance at a time (:37-43), so the convolutions
@@ -1221,9 +1382,11 @@ def test(model, testset, device, *, batch_size=1, whole_utterances=False, decode
     return wer(references, predictions)
 
 
-def train_model(trainset, devset, device, n_epochs=200, *, compute_dtype=torch.bfloat16, f32_matmul='exact', max_steps=None):
+def train_model(trainset, devset, device, n_epochs=200, *, compute_dtype=torch.bfloat16, f32_matmul='exact', max_steps=None, mwer=None):
     """:61-117 on the MI355X: batches under a 128 000-sample budget, AdamW (lr 3e-4 in the reference's flags), linear
-    warm-up, an optimiser step every SECOND batch (gradients accumulate in the flat .grad arena), MultiStepLR."""
+    warm-up, an optimiser step every SECOND batch (gradients accumulate in the flat .grad arena), MultiStepLR.
+    mwer=dict(space=.., n_best=.., ...): the criterion is mwer_loss with these keywords (sequence-discriminative second stage, usually started
+    from a CTC-trained model through the start_training_from flag) in place of ctc_loss; None (default): the step is the reference's."""
     dataloader = torch.utils.data.DataLoader(trainset, collate_fn=devset.collate_raw, num_workers=0, batch_sampler=SizeAwareSampler(trainset, 128000))
     n_chars = len(devset.text_transform.chars)
     model = Model(devset.num_features, n_chars + 1, compute_dtype=compute_dtype, f32_matmul=f32_matmul).to(device)
@@ -1254,7 +1417,7 @@ def train_model(trainset, devset, device, n_epochs=200, *, compute_dtype=torch.b
             schedule_lr(batch_idx)
             X, X_raw, sess = prepare_batch(batch, device, loss_plan=False)
             pred = model(X, X_raw, sess)
-            loss = ctc_loss(pred, batch, blank=n_chars)
+            loss = ctc_loss(pred, batch, blank=n_chars) if mwer is None else mwer_loss(pred, batch, **dict({'blank': n_chars}, **mwer))
             losses.append(loss.detach())
             loss.backward()
             if (batch_idx + 1) % 2 == 0:

@@ -249,6 +249,130 @@ def _ctc_bwd(ctx, g_loss, g_dl, g_nll, g_amax):
 ctc_loss.register_autograd(_ctc_bwd, setup_context=_ctc_setup)
 
 
+# ------------------------------------------------------------------------------------------------ ctc_nbest_logp / nbest_expected_risk
+def _nbest_tables(name, logits, utt, hyp, targets):
+    dev = logits.device
+    if logits.dim() != 2 or logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise RuntimeError('%s: logits must be a contiguous (frames, ld) float32 matrix' % name)
+    if utt.dim() != 2 or utt.shape[1] != 4 or utt.dtype != torch.int64 or not utt.is_contiguous() or utt.device != dev:
+        raise RuntimeError('%s: utt must be a contiguous (n, 4) int64 table on the device of the logits' % name)
+    if hyp.dim() != 2 or hyp.shape[1] != 3 or hyp.dtype != torch.int64 or not hyp.is_contiguous() or hyp.device != dev:
+        raise RuntimeError('%s: hyp must be a contiguous (n, 3) int64 table on the device of the logits' % name)
+    if targets.dim() != 1 or targets.dtype != torch.int32 or not targets.is_contiguous() or targets.device != dev:
+        raise RuntimeError('%s: targets must be a contiguous flat int32 tensor on the device of the logits' % name)
+
+
+@torch.library.custom_op('silent_speech::ctc_nbest_logp', mutates_args=())
+def ctc_nbest_logp(logits: Tensor, utt: Tensor, hyp: Tensor, targets: Tensor, max_s: int, ws_floats: int, V: int, blank: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """Full-sum CTC log-likelihood of several label strings per utterance (ss_ctc_nbest_logp in include/silent_speech_hip.h states the
+    definition).  logits [M][ld >= V] f32 raw model outputs; utt [n][4] int64 = (first frame, frames, first hypothesis, K); hyp [H][3] int64 =
+    (first label in targets, S, workspace offset in floats); targets int32; max_s >= the longest hypothesis, ws_floats = the sum of the
+    T (2 S + 1) blocks.  Returns (logp [H] f32, per-frame lse [M], the workspace the backward pass reads)."""
+    _nbest_tables('ctc_nbest_logp', logits, utt, hyp, targets)
+    dev = logits.device
+    M, ld = logits.shape
+    H = hyp.shape[0]
+    st = _lib.stream_of(logits)
+    ws_bytes = _L().ss_ctc_nbest_workspace_bytes(H, ws_floats)
+    if ws_bytes < 0:
+        raise RuntimeError('ctc_nbest_logp: %d hypotheses with %d workspace floats' % (H, ws_floats))
+    lse = torch.empty(max(M, 1), dtype=torch.float32, device=dev)
+    amax = torch.empty(max(M, 1), dtype=torch.int32, device=dev)
+    if M:
+        _lib.check(_L().ss_frame_lse(_p(logits), ld, 0, V, M, _p(lse), _p(amax), st), 'ss_frame_lse')
+    ws = torch.empty(ws_bytes // 8 + 1, dtype=torch.int64, device=dev)
+    logp = torch.empty(H, dtype=torch.float32, device=dev)
+    _lib.check(_L().ss_ctc_nbest_logp(_p(logits) if M else None, ld, V, blank, M, _p(lse), _p(utt) if utt.shape[0] else None, utt.shape[0],
+                                      _p(hyp) if H else None, H, max_s, _p(targets) if targets.shape[0] else None, targets.shape[0], _p(ws), ws_floats,
+                                      _p(logp) if H else None, st), 'ss_ctc_nbest_logp')
+    return logp, lse, ws
+
+
+@ctc_nbest_logp.register_fake
+def _(logits, utt, hyp, targets, max_s, ws_floats, V, blank):
+    return (logits.new_empty(hyp.shape[0]), logits.new_empty(max(logits.shape[0], 1)),
+            logits.new_empty(torch.library.get_ctx().new_dynamic_size(), dtype=torch.int64))
+
+
+@torch.library.custom_op('silent_speech::ctc_nbest_backward', mutates_args=())
+def ctc_nbest_backward(logits: Tensor, lse: Tensor, utt: Tensor, hyp: Tensor, targets: Tensor, ws: Tensor, logp: Tensor, g: Tensor,
+                       ws_floats: int, V: int, blank: int) -> Tensor:
+    """d (sum_h g_h logp_h) / d logits for the outputs of ctc_nbest_logp (ss_ctc_nbest_backward): every row of the result is written."""
+    _nbest_tables('ctc_nbest_backward', logits, utt, hyp, targets)
+    M, ld = logits.shape
+    H = hyp.shape[0]
+    g = g.to(torch.float32).contiguous()
+    if g.shape != (H,) or logp.shape != (H,):
+        raise RuntimeError('ctc_nbest_backward: %d cotangents for %d hypotheses' % (g.numel(), H))
+    dlogits = torch.empty_like(logits)
+    _lib.check(_L().ss_ctc_nbest_backward(_p(logits) if M else None, ld, V, blank, M, _p(lse), _p(utt) if utt.shape[0] else None, utt.shape[0], H,
+                                          _p(targets) if targets.shape[0] else None, _p(ws), ws_floats, _p(logp) if H else None, _p(g) if H else None,
+                                          _p(dlogits) if M else None, _lib.stream_of(logits)), 'ss_ctc_nbest_backward')
+    return dlogits
+
+
+@ctc_nbest_backward.register_fake
+def _(logits, lse, utt, hyp, targets, ws, logp, g, ws_floats, V, blank):
+    return torch.empty_like(logits)
+
+
+def _ctc_nbest_setup(ctx, inputs, output):
+    logits, utt, hyp, targets, max_s, ws_floats, V, blank = inputs
+    ctx.save_for_backward(logits, utt, hyp, targets, output[0], output[1], output[2])
+    ctx.nbest_args = (ws_floats, V, blank)
+
+
+def _ctc_nbest_bwd(ctx, g_logp, g_lse, g_ws):
+    logits, utt, hyp, targets, logp, lse, ws = ctx.saved_tensors
+    ws_floats, V, blank = ctx.nbest_args
+    if g_logp is None:
+        g_logp = torch.zeros_like(logp)
+    return (ctc_nbest_backward(logits, lse, utt, hyp, targets, ws, logp, g_logp, ws_floats, V, blank),) + (None,) * 7
+
+
+ctc_nbest_logp.register_autograd(_ctc_nbest_bwd, setup_context=_ctc_nbest_setup)
+
+
+@torch.library.custom_op('silent_speech::nbest_expected_risk', mutates_args=())
+def nbest_expected_risk(logp: Tensor, cost: Tensor, groups: Tensor, scale: float) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """Expected risk of n-best lists under their own posterior softmax(scale logp) (ss_nbest_expected_risk in include/silent_speech_hip.h):
+    logp, cost [H] f32; groups [n][2] int64 = (first hypothesis, K <= 128).  Returns (loss [1] f32 = the mean risk over the lists that have a
+    finite entry, risk [n] f64, post [H] f32, dlogp [H] f32 = d loss / d logp); autograd reaches logp through dlogp."""
+    dev = logp.device
+    H, ng = logp.shape[0], groups.shape[0]
+    if logp.dim() != 1 or logp.dtype != torch.float32 or cost.shape != logp.shape or cost.dtype != torch.float32 or cost.device != dev:
+        raise RuntimeError('nbest_expected_risk: logp and cost must be float32 vectors of one length on one device')
+    if groups.dim() != 2 or groups.shape[1] != 2 or groups.dtype != torch.int64 or not groups.is_contiguous() or groups.device != dev:
+        raise RuntimeError('nbest_expected_risk: groups must be a contiguous (n, 2) int64 table (first hypothesis, K) on the device of logp')
+    if ng > 65535:
+        raise RuntimeError('nbest_expected_risk: %d lists (at most 65535 in one call)' % ng)
+    logp, cost = logp.contiguous(), cost.contiguous()
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    risk = torch.empty(ng, dtype=torch.float64, device=dev)
+    post = torch.empty(H, dtype=torch.float32, device=dev)
+    dlogp = torch.empty(H, dtype=torch.float32, device=dev)
+    _lib.check(_L().ss_nbest_expected_risk(_p(logp) if H else None, _p(cost) if H else None, H, _p(groups) if ng else None, ng, scale, _p(loss),
+                                           _p(risk) if ng else None, _p(post) if H else None, _p(dlogp) if H else None, _lib.stream_of(logp)),
+               'ss_nbest_expected_risk')
+    return loss, risk, post, dlogp
+
+
+@nbest_expected_risk.register_fake
+def _(logp, cost, groups, scale):
+    return logp.new_empty(1), logp.new_empty(groups.shape[0], dtype=torch.float64), torch.empty_like(logp), torch.empty_like(logp)
+
+
+def _nbest_risk_setup(ctx, inputs, output):
+    ctx.save_for_backward(output[3])
+
+
+def _nbest_risk_bwd(ctx, g_loss, g_risk, g_post, g_dlogp):
+    return ctx.saved_tensors[0] * g_loss, None, None, None
+
+
+nbest_expected_risk.register_autograd(_nbest_risk_bwd, setup_context=_nbest_risk_setup)
+
+
 # ------------------------------------------------------------------------------------------------ ctc_beam_search (inference only: no autograd)
 def _beam_search_checks(name, min_classes, logits, utt, V, blank, total_frames, max_len, beam_width, n_best):
     """The argument checks ctc_beam_search and ctc_word_beam_search share."""
